@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """Depth Pro frames/sec at 1536x1536 on 1..8 MI355X (one process per GPU).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line.  `--dump-outputs DIR`
+also writes what the last timed step returned as DIR/<name>.npy.  `--full` adds the legs that take
+runs of their own: per-kernel / roofline figures, depth parity vs the reference, the CPU baseline.
 
 A step = every rank runs `DepthPro.infer(transform(frame))` on one synthetic 1536x1536
 uint8 frame that is already resident in HBM (transform: u8 -> normalised fp32 on the GPU;
@@ -123,6 +127,33 @@ def depth_parity(depth: torch.Tensor, canonical: torch.Tensor, fov: torch.Tensor
             "fov_rel_err": round(abs(float(fov.reshape(-1)[0]) - fov_ref) / fov_ref, 7),
             "target": 1e-3, "frame": "synthetic frame 0 (1536x1536), graph replay, every 8th pixel",
             "reference": "tests/golden/golden_forward_frame0.npz"}
+
+
+DUMP_BUDGET = 64 << 20          # bytes of .npy data per --dump-outputs directory
+
+
+def dump_outputs(path: str, pred: dict, gathered=None) -> None:
+    """--dump-outputs: what the last timed step returned to its caller, as <path>/<name>.npy (float32).
+
+    `pred` is that step's `DepthPro.infer` result on this rank (depth map + focal length); `gathered`
+    (N > 1) the depth maps rank 0 received for that step, in rank order.  When the gathered maps
+    would not fit DUMP_BUDGET beside the rest, a fixed seeded sample of their pixels (the same
+    pixels of every map, from default_rng(0)) is written with its flat indices."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {name: t.detach().float().cpu().numpy() for name, t in pred.items()}
+    if gathered is not None:
+        maps = np.stack([t.detach().float().cpu().numpy() for t in gathered])
+        room = DUMP_BUDGET - sum(a.nbytes for a in arrays.values())
+        per_map = maps[0].size
+        keep = room // (maps.shape[0] * 4 + 8)         # float32 per map + one int64 index
+        if keep < per_map:
+            idx = np.sort(np.random.default_rng(seed=0).choice(per_map, size=keep, replace=False))
+            arrays["depth_gathered_index"] = idx.astype(np.float64)
+            maps = maps.reshape(maps.shape[0], -1)[:, idx]
+        arrays["depth_gathered"] = maps
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BUDGET
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cpu_model() -> str:
@@ -266,7 +297,12 @@ def main():
                     help="compute precision: bf16 / fp16 everywhere, or mixed = bf16 ViTs + f16 maps, "
                          "decoder and heads (depth_pro.depth_pro.PRECISION_MODES)")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned (rank 0) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: per-kernel / roofline timing, depth "
+                         "parity vs the reference, and (1 GPU, unless --no-cpu-baseline) the CPU baseline")
     ap.add_argument("--pool", type=int, default=4, help="distinct resident frames per rank")
     ap.add_argument("--ab", action="store_true",
                     help="A/B timing run (tools/ab_env.sh): allows the AB_KNOBS switches off their defaults and reports "
@@ -325,9 +361,16 @@ def main():
         # the engine input, graph replay of the forward, depth / focal-length epilogue, status)
         with torch.no_grad():
             pred = model.infer(transform(frames[n % len(frames)]))
+        last["pred"] = pred
         return pred["depth"], model.last_status()
 
-    run = timed_steps(infer_one, args.steps, args.warmup, world, dev)
+    def keep_gathered(n, bufs):
+        last["gathered"] = bufs          # step n's depth maps at rank 0; the final call is the last timed step's
+
+    last = {}
+    dump = args.dump_outputs and rank == 0
+    run = timed_steps(infer_one, args.steps, args.warmup, world, dev,
+                      on_gathered=keep_gathered if dump and world > 1 else None)
     elapsed, statuses = run["elapsed"], run["statuses"]
     frames_total = run["frames_total"]
     fps = frames_total / elapsed
@@ -340,6 +383,12 @@ def main():
         refuse(f"rank {rank}: {len(bad)} of {len(statuses)} benched infer calls invalid "
                f"(first: {bad[0].error()})", 5)
 
+    if dump:
+        dump_outputs(args.dump_outputs, last["pred"], last.get("gathered"))
+
+    # --full: the legs beside the headline figure (rank 0), each a run of its own after the timed steps
+    full = args.full and rank == 0
+
     # per-kernel leg (rank 0): instrumented eager frames with HIP events on the launching stream
     # around every launch, grouped by (kernel kind, shape).  `groups`: a SERIAL frame (every launch on
     # one stream, alone on the chip -- as in a rocprofv3 kernel trace, which serialises the graph's
@@ -350,7 +399,7 @@ def main():
     # reported for the dominant kernel only, as its in-frame figure.
     groups, groups_cc = {}, {}
     serial_frame_ms = None
-    if rank == 0:
+    if full:
         ops.normalize_u8(frames[0], eng.x0)
         for _ in range(2):
             eng.forward()                   # warm (no graph)
@@ -372,7 +421,7 @@ def main():
         eng.serial_side = False
 
     parity = None
-    if rank == 0:
+    if full:
         # frame 0 through the API (graph replay) against the reference's output
         x = transform(frames[0])
         with torch.no_grad():
@@ -387,7 +436,7 @@ def main():
         if not args.ab and not parity["depth_rel_l1"] < parity["target"]:
             refuse(f"depth rel-L1 {parity['depth_rel_l1']} >= {parity['target']} vs the reference", 4)
 
-    if rank == 0:
+    if full:
         achieved = fps_per_gpu * FLOP_PER_FRAME / 1e12
         kern = {}
         for (kind, shape, _), g in groups.items():
@@ -432,6 +481,8 @@ def main():
                 # same kernel in the committed rocprofv3 summary (every launch of it in that bench run)
                 dom_info["rocprof"] = {"source": PROF_STATS, "avg_us": round(rp[0], 2), "calls": rp[1],
                                        "frac": round(dom_flop / (rp[0] * 1e-6) / 1e12 / PEAK_BF16_TFLOPS, 4)}
+
+    if rank == 0:
         out = {
             "metric": "frames/sec at 1536x1536 (1/2/4/8 MI355X) + depth L1 vs reference",
             "value": round(fps, 3),
@@ -457,6 +508,10 @@ def main():
                                               "int8 lo part, ~16 significant bits, the side encoders' in "
                                               "fp32): the default, chosen to meet depth L1 < 1e-3"
                                      }[args.dtype]},
+            "setup_s": round(t_setup, 1),
+        }
+    if full:
+        out.update({
             # dominant kernel: algorithmic FLOP per launch / its average HIP-event duration
             "roofline": {"bound": "mfma", "achieved": round(dom_tf, 1), "peak": PEAK_BF16_TFLOPS,
                          "unit": "TFLOP/s", "frac": round(dom_tf / PEAK_BF16_TFLOPS, 4),
@@ -472,13 +527,13 @@ def main():
                               "serial_frame_ms": round(serial_frame_ms, 3),
                               "serial_frame_kernel_ms": round(sum(k["ms"] for k in kern.values()), 3)},
             "parity": parity,
-            "setup_s": round(t_setup, 1),
-        }
+        })
+    if rank == 0:
         if args.ab:        # A/B timing run: not a bench result
             out["metric"] = "A/B timing run (DP_GEMM_DEBUG / DP_ABLATE allowed): not a bench result"
             out["ab_fps"], out["value"] = out["value"], None
             out["ab_env"] = {v: os.environ.get(v, "") for v in AB_KNOBS}
-        elif world == 1 and not args.no_cpu_baseline:
+        elif full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if world > 1:

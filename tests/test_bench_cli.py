@@ -51,6 +51,36 @@ def test_ablation_or_debug_switch_refused(env):
     assert line.get("value") is None and "use --ab" in line["error"]
 
 
+def test_dump_outputs_writes_float32_arrays_within_budget(tmp_path):
+    """bench.dump_outputs (--dump-outputs): the last step's infer result as <name>.npy in float32;
+    gathered maps (N > 1) whole when they fit the 64 MB budget, else the same seeded sample of
+    every map's pixels with its flat indices, identical from call to call."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, REPO)
+    import bench
+
+    g = torch.Generator().manual_seed(0)
+    pred = {"depth": torch.rand(1536, 1536, generator=g), "focallength_px": torch.tensor(1300.0)}
+    bench.dump_outputs(str(tmp_path / "one"), pred)
+    assert sorted(os.listdir(tmp_path / "one")) == ["depth.npy", "focallength_px.npy"]
+    d = np.load(tmp_path / "one" / "depth.npy")
+    assert d.dtype == np.float32 and np.array_equal(d, pred["depth"].numpy())
+
+    maps = [torch.rand(1536, 1536, generator=g) for _ in range(8)]
+    bench.dump_outputs(str(tmp_path / "two"), pred, maps[:2])
+    assert np.array_equal(np.load(tmp_path / "two" / "depth_gathered.npy")[1], maps[1].numpy())
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), pred, maps)
+    arrays = {f: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    idx = arrays["depth_gathered_index.npy"].astype(np.int64)
+    assert np.array_equal(arrays["depth_gathered.npy"][5], maps[5].numpy().reshape(-1)[idx])
+    assert np.array_equal(np.load(tmp_path / "b" / "depth_gathered_index.npy"), arrays["depth_gathered_index.npy"])
+
+
 def _timed_worker(rank, world, port, q):
     """One rank of bench.timed_steps over gloo with a stub model: frame k -> rank k mod world, the
     depth map of global frame k is a (3, 5) map filled with k; rank 1 is slower per frame."""

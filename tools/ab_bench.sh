@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 for R in 1 2; do
   for F in "$@"; do
-    DP_GEMM_DEBUG=$F timeout -k 10 300 python -u bench.py --ab --no-cpu-baseline --steps 40 > $OUT/ab_${F}_$R.json 2> $OUT/ab_${F}_$R.err
+    DP_GEMM_DEBUG=$F timeout -k 10 300 python -u bench.py --ab --full --no-cpu-baseline --steps 40 > $OUT/ab_${F}_$R.json 2> $OUT/ab_${F}_$R.err
   done
 done
 python - "$OUT" <<'PY'

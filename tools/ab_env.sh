@@ -10,7 +10,7 @@ for R in 1 2; do
   i=0
   for E in "$@"; do
     i=$((i + 1))
-    env $E timeout -k 10 300 python -u bench.py --ab --no-cpu-baseline --steps 40 > $OUT/ab_${i}_$R.json 2> $OUT/ab_${i}_$R.err
+    env $E timeout -k 10 300 python -u bench.py --ab --full --no-cpu-baseline --steps 40 > $OUT/ab_${i}_$R.json 2> $OUT/ab_${i}_$R.err
   done
 done
 python tools/ab_summary.py "$OUT" "$@" | tee $OUT/ab.txt

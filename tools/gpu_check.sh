@@ -19,10 +19,10 @@ for S in $STEPS; do
     smoke)
       timeout -k 10 300 python -u -c 'import __graft_entry__ as g; g.smoke()' > $OUT/smoke.log 2>&1 ;;
     bench)
-      timeout -k 10 400 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err ;;
+      timeout -k 10 400 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err ;;
     prof)
       timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof -o prof --output-format csv \
-        -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > $OUT/prof.log 2>&1 ;;
+        -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $OUT/prof.log 2>&1 ;;
     pmc)
       # separate passes (FETCH_SIZE takes 3 TCC slots, WRITE_SIZE 2); eager forward so every dispatch is attributed
       timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o pmc \
@@ -57,8 +57,8 @@ for S in $STEPS; do
         --alone-md $OUT/kernel_alone.md > /dev/null ;;
     side)
       # side-encoder cost by ablation (DP_ABLATE=side: image / FOV encoders skipped) vs the full frame
-      DP_ABLATE=side timeout -k 10 300 python -u bench.py --ab --no-cpu-baseline --steps 40 > $OUT/bench_noside.json 2> $OUT/bench_noside.err
-      timeout -k 10 300 python -u bench.py --no-cpu-baseline --steps 40 > $OUT/bench_side.json 2> $OUT/bench_side.err ;;
+      DP_ABLATE=side timeout -k 10 300 python -u bench.py --ab --full --no-cpu-baseline --steps 40 > $OUT/bench_noside.json 2> $OUT/bench_noside.err
+      timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --steps 40 > $OUT/bench_side.json 2> $OUT/bench_side.err ;;
     loop)
       # the video loop as users run it (configs 3 and 5): PNG frames -> GPU -> PNG (+ PLY)
       timeout -k 10 400 python -u tools/loop_bench.py --frames 64 --size 1536x1536 > $OUT/loop_1536.log 2>&1

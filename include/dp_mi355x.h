@@ -41,7 +41,7 @@ enum { DP_A_DENSE = 0, DP_A_CONV = 1 };
 enum { DP_STORE_ROWS = 0, DP_STORE_DECONV2X2 = 1, DP_STORE_HEAD_PS = 2 };
 
 /* ABI version of this header; the Python loader refuses a mismatching .so. */
-#define DP_ABI_VERSION 14
+#define DP_ABI_VERSION 15
 int dp_abi_version(void);
 
 /*
@@ -408,6 +408,117 @@ int dp_depth_to_points(const float* depth, int32_t H, int32_t W, const float* f_
 enum { DP_DEPTH_IMG_COLOR = 0, DP_DEPTH_IMG_RAW16 = 1 };
 int dp_depth_to_image(const float* depth, int64_t n, uint32_t* minmax, const uint8_t* lut, int32_t lut_n,
                       int32_t mode, void* out, dp_stream_t stream);
+
+/*
+ * ---- Ground-normalised point clouds (ABI 15, csrc/dp_ground.hip) ---------------------------------
+ * The first stage of the reference's 3-D pipeline after depth_to_3d: ground-plane fit, levelling
+ * and per-cell adjustment (img_to_normalized_pointcloud.py:601-816, :880-981, :983-1118).  All fp64,
+ * each product and sum rounded on its own (no FMA) as numpy's ufuncs do; all on the caller's
+ * stream, no synchronisation and no host read-back.
+ *
+ * Common conventions of every entry below:
+ *   points     fp64 [n_max][3] device rows (x, y, z), as dp_depth_to_points writes them.
+ *   n_dev      device int32: the first *n_dev rows are live (clamped to [0, n_max]); NULL: n_max.
+ *              n_max < 2^31.  n_max = 0 (or *n_dev = 0) is valid: no point is touched, counts are 0.
+ *   workspace  >= dp_ground_workspace_size(n_max) bytes of device memory, 8-byte aligned, owned by
+ *              the call until the stream has passed it (its content need not be initialised).
+ *   A point with a NaN or +-inf coordinate belongs to no segment anywhere, is counted in the
+ *   "non-finite" output and is copied to points_out unchanged.  (The reference is undefined for
+ *   such points -- its np.min / np.percentile would propagate them; this behaviour is ours.)
+ */
+#define DP_GROUND_MAX_SEG 1024   /* segments of one selection (32 x 32 grid cells) */
+#define DP_GROUND_MAX_GRID 32    /* grid_size of the trace and of the adjustment */
+int64_t dp_ground_workspace_size(int64_t n_max);
+
+/*
+ * dp_seg_select: order statistic of fp64 keys per segment (np.percentile / the k-th smallest of
+ * np.partition), the primitive under every stage below.  keys[i * key_stride] (i < n) is the key of
+ * element i, seg[i] in [0, n_seg) its segment, any other id (-1) "in no segment"; n_seg <= 1024.
+ * Keys must not be NaN; -0.0 counts (and is returned) as +0.0.
+ *   mode DP_SEL_PERCENTILE: values_out[s] = np.percentile(keys of s, param) with method="linear":
+ *     v = (count - 1) * (param / 100), a, b = the floor(v)-th and next smallest, t = v - floor(v),
+ *     a + (b - a) * t, replaced by b - (b - a) * (1 - t) where t >= 0.5 (numpy's _lerp).
+ *   mode DP_SEL_KTH: values_out[s] = the k-th smallest key (1-based),
+ *     k = min(count, max(kmin, (int)(param * count))) -- derived on the device from the count.
+ * A segment takes part only if count > min_count (and count > 0); otherwise values_out[s] = NaN.
+ * counts_out[s] (int32) = keys in segment s, always.  Selection is by most-significant-digit radix
+ * passes (8 bits) over per-(segment, digit) histograms of order-preserving 64-bit keys; nothing is
+ * sorted, and any number of equal keys costs the same.
+ */
+enum { DP_SEL_PERCENTILE = 0, DP_SEL_KTH = 1 };
+int dp_seg_select(const double* keys, int64_t key_stride, const int32_t* seg, const int32_t* n_dev,
+                  int32_t n_max, int32_t n_seg, int32_t mode, double param, int32_t kmin, int32_t min_count,
+                  int32_t* counts_out, double* values_out, void* workspace, int64_t workspace_bytes,
+                  dp_stream_t stream);
+
+/*
+ * dp_ground_trace: the ground trace of grid_based_ground_plane_fit with initial_ground_model=None
+ * (img_to_normalized_pointcloud.py:629-700): z min / max, bin_edges = np.linspace(z_min, z_max,
+ * grid_size + 1), bin = np.digitize(z, bin_edges) - 1 (so z == z_max falls outside every bin, as
+ * in the reference); each bin with more than 10 points contributes the mean of its
+ * max(1, int(0.05 * count)) lowest-y points, ties at the cut taken in index order.
+ *   trace_out  fp64 [grid_size][4]: mean x, y, z and the bin's point count
+ *   valid_out  int32 [grid_size]: 1 where the bin contributed
+ *   info_out   fp64 [4]: finite points, non-finite points, z_min, z_max
+ * grid_size <= 32.
+ */
+int dp_ground_trace(const double* points, const int32_t* n_dev, int32_t n_max, int32_t grid_size,
+                    double* trace_out, int32_t* valid_out, double* info_out, void* workspace,
+                    int64_t workspace_bytes, dp_stream_t stream);
+
+/*
+ * dp_ground_lowest: the fit's fallback trace (:702-707): the max(10, int(0.05 * count)) lowest-y
+ * finite points (all of them if there are fewer), ties at the cut in index order.
+ *   points_out fp64 [capacity][3], index_out int32 [capacity]: the selected points and their row
+ *              indices, in no particular order (sort by index for the reference's order up to ties);
+ *              capacity >= max(10, int(0.05 * n_max)) holds them all, extra ones are dropped.
+ *   info_out   fp64 [2]: number selected, finite points
+ */
+int dp_ground_lowest(const double* points, const int32_t* n_dev, int32_t n_max, double* points_out,
+                     int32_t* index_out, int32_t capacity, double* info_out, void* workspace,
+                     int64_t workspace_bytes, dp_stream_t stream);
+
+/*
+ * dp_ground_dist_percentile: the fit's "push the plane down" inputs (:771-784): signed distances
+ * dist = x*n0 + y*n1 + z*n2 + d of the finite points to plane = {n0, n1, n2, d} (host pointer),
+ * their np.percentile(q) and the number below the plane.
+ *   out fp64 [4]: percentile (NaN without points), points with dist < 0, finite points, non-finite
+ */
+int dp_ground_dist_percentile(const double* points, const int32_t* n_dev, int32_t n_max, const double* plane,
+                              double q, double* out, void* workspace, int64_t workspace_bytes,
+                              dp_stream_t stream);
+
+/*
+ * dp_ground_normalize: normalize_point_cloud_to_ground (:880-981).  model (host pointer, fp64 [15]):
+ *   [0..2] unit normal, [3] d  (dist = p . n + d, point_plane_distances :858-878)
+ *   [4..12] R row-major, [13] const, [14] rotate flag -- R (Rodrigues, :917-934) and
+ *   const = -d / (R n)[1] are the caller's fp64 host values; flag 0 is the reference's
+ *   |n . y| > 0.99 branch: the points are copied, R and const unused.
+ * Per finite point p' = R p, y' -= const; ground level = np.percentile(y' of the points with
+ * |dist| < 0.1, 2), subtracted only if there are more than 10 such points; then ground points
+ * (|dist| < 0.05) with y' < 0 go to 0 and the others with y' < -0.1 go to -0.1.
+ *   points_out fp64 [n_max][3] (must not alias points)
+ *   stats_out  fp64 [8]: finite points, non-finite points, points with |dist| < 0.1, ground level
+ *              (0 if not taken), level taken (0 / 1), ground points, set to 0, limited to -0.1
+ *              (the last three are the reference's printed counts)
+ */
+int dp_ground_normalize(const double* points, double* points_out, const int32_t* n_dev, int32_t n_max,
+                        const double* model, double* stats_out, void* workspace, int64_t workspace_bytes,
+                        dp_stream_t stream);
+
+/*
+ * dp_ground_adjust: grid_based_ground_adjustment (:983-1118).  x / z min and max, np.linspace edges
+ * (start + i * step, last edge = stop), cell = clip(digitize - 1) per axis, x_idx * grid_size +
+ * z_idx.  A cell is adjusted if it has >= 10 points, >= 5 of them with y < 0.2, and
+ * p = np.percentile(those y, percentile) > 0.01; its points then lose p (y < 0.1),
+ * p * (1 - (y - 0.1) / 1.4) (0.1 <= y < 1.5) or nothing, and are clamped at 0.
+ *   points_out fp64 [n_max][3] (must not alias points); grid_size <= 32
+ *   stats_out  fp64 [8]: finite points, non-finite points, non-empty cells, cells with >= 10 points,
+ *              cells adjusted, points adjusted (the reference's four summary numbers), 0, 0
+ */
+int dp_ground_adjust(const double* points, double* points_out, const int32_t* n_dev, int32_t n_max,
+                     int32_t grid_size, double percentile, double* stats_out, void* workspace,
+                     int64_t workspace_bytes, dp_stream_t stream);
 
 #ifdef __cplusplus
 }

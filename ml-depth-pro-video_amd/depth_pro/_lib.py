@@ -27,7 +27,9 @@ INTERP_MODES = {"bilinear": DP_INTERP_BILINEAR, "bicubic": DP_INTERP_BICUBIC}
  DP_TILE_BIG_512x128, DP_TILE_PBIG_320x256, DP_TILE_PBIG_256x256, DP_TILE_DUAL_256x128,
  DP_TILE_P8PH_256x256, DP_TILE_8PH_320x256, DP_TILE_CV3_256x256, DP_TILE_SPLITK_256x256,
  DP_TILE_CV3_192x256, DP_TILE_CV3_384x128) = range(24)
-DP_ABI_VERSION = 14
+DP_SEL_PERCENTILE, DP_SEL_KTH = 0, 1
+DP_GROUND_MAX_SEG, DP_GROUND_MAX_GRID = 1024, 32
+DP_ABI_VERSION = 15
 
 _ERRORS = {1000: "DP_ERR_ARG", 1001: "DP_ERR_SHAPE", 1002: "DP_ERR_ALIGN", 1003: "DP_ERR_DTYPE"}
 
@@ -42,6 +44,8 @@ EXPORTS = (
     "dp_resize_bilinear", "dp_resize", "dp_patchify_pyramid", "dp_vit_cls_rows", "dp_merge_windows",
     "dp_merge_windows_range", "dp_fov_tail", "dp_infer_epilogue", "dp_infer_epilogue_mode", "dp_gemm_workspace_size", "dp_gemm_plan",
     "dp_depth_to_points", "dp_gemm_workspace_check", "dp_resize_u8_cv", "dp_depth_to_image",
+    "dp_ground_workspace_size", "dp_seg_select", "dp_ground_trace", "dp_ground_lowest", "dp_ground_dist_percentile",
+    "dp_ground_normalize", "dp_ground_adjust",
 )
 
 
@@ -125,12 +129,20 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "dp_depth_to_points": [vp, i32, i32, vp, f64, i32, vp, vp, vp, vp, vp],
         "dp_depth_to_image": [vp, i64, vp, vp, i32, i32, vp, vp],
         "dp_gemm_plan": [ctypes.POINTER(GemmArgs), ctypes.POINTER(i32), ctypes.POINTER(i32)],
+        "dp_ground_workspace_size": [i64],
+        "dp_seg_select": [vp, i64, vp, vp, i32, i32, i32, f64, i32, i32, vp, vp, vp, i64, vp],
+        "dp_ground_trace": [vp, vp, i32, i32, vp, vp, vp, vp, i64, vp],
+        "dp_ground_lowest": [vp, vp, i32, vp, vp, i32, vp, vp, i64, vp],
+        "dp_ground_dist_percentile": [vp, vp, i32, ctypes.POINTER(f64), f64, vp, vp, i64, vp],
+        "dp_ground_normalize": [vp, vp, vp, i32, ctypes.POINTER(f64), vp, vp, i64, vp],
+        "dp_ground_adjust": [vp, vp, vp, i32, i32, f64, vp, vp, i64, vp],
     }
     for name, argtypes in sig.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = ctypes.c_int
     lib.dp_gemm_workspace_size.restype = ctypes.c_int64
+    lib.dp_ground_workspace_size.restype = ctypes.c_int64
     lib.dp_gemm_debug_flags.argtypes = [ctypes.c_int]
     lib.dp_gemm_debug_flags.restype = ctypes.c_int
     ver = lib.dp_abi_version()

@@ -5,12 +5,20 @@ Open3D PLY write (`o3d.io.write_point_cloud`, :1318).  The back-projection and t
 row-major compaction of the valid pixels run in `dp_depth_to_points` (HIP, fp64 as
 numpy computes it); the PLY writer is this package's own (no Open3D): binary
 little-endian, `double x y z` + `uchar red green blue`, the vertex layout Open3D writes.
-The reference's ground-plane normalisation / RANSAC / floor plans are out of scope.
+
+Ground normalisation (the rest of the reference's first 3-D stage, same file): `fit_ground_plane`
+(`grid_based_ground_plane_fit`, :601-816), `normalize_to_ground` (`normalize_point_cloud_to_ground`,
+:880-981), `ground_adjust` (`grid_based_ground_adjustment`, :983-1118), the `ground.json` helpers
+(:225-312) and `apply_rotation_to_plane` (:314-373).  All per-point work and every percentile run
+in csrc/dp_ground.hip (segmented radix selection, fp64); the host only sees the <= 32 trace points.
+Not built: `optimize_ground_plane` (scipy) and the 50 000-point random pre-sample in front of it.
 """
 
 from __future__ import annotations
 
 import ctypes
+import json
+import os
 from typing import Optional, Tuple, Union
 
 import numpy as np
@@ -134,3 +142,279 @@ def read_ply(path: str) -> Tuple[np.ndarray, Optional[np.ndarray]]:
         rec = np.frombuffer(data[end:], dtype=[("p", "<f8", 3), ("c", "u1", 3)], count=n)
         return rec["p"].copy(), rec["c"].copy()
     return np.frombuffer(data[end:], dtype="<f8", count=3 * n).reshape(n, 3).copy(), None
+
+
+# ---- ground-plane fit, levelling, grid adjustment (csrc/dp_ground.hip) ---------------------------
+
+MAX_GRID = _lib.DP_GROUND_MAX_GRID
+
+
+def _ground_args(points: torch.Tensor, count):
+    if points.device.type != "cuda":
+        raise _lib.DPError("ground normalisation runs on the ROCm device (csrc/dp_ground.hip)")
+    if points.dtype != torch.float64 or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("points must be an (N, 3) float64 tensor")
+    pts = points.contiguous()
+    n = pts.shape[0]
+    if n >= 2 ** 31:
+        raise ValueError("at most 2^31 - 1 points")
+    if count is not None:
+        if not torch.is_tensor(count):
+            count = torch.tensor([int(count)], dtype=torch.int32, device=pts.device)
+        count = count.detach().to(device=pts.device, dtype=torch.int32).reshape(1)
+    lib = _lib.load()
+    ws = torch.empty(int(lib.dp_ground_workspace_size(n)), dtype=torch.uint8, device=pts.device)
+    stream = torch.cuda.current_stream(pts.device).cuda_stream
+    return lib, pts, n, count, (None if count is None else count.data_ptr()), ws, stream
+
+
+def _check_grid(grid_size: int) -> int:
+    g = int(grid_size)
+    if not 1 <= g <= MAX_GRID:
+        raise ValueError(f"grid_size must be in [1, {MAX_GRID}] (got {grid_size})")
+    return g
+
+
+def segmented_select(keys: torch.Tensor, seg: torch.Tensor, n_seg: int, *, q: Optional[float] = None,
+                     frac: Optional[float] = None, kmin: int = 1, min_count: int = 0, count=None):
+    """Order statistic per segment on the device (`dp_seg_select`), asynchronous.
+
+    keys: (n,) float64, seg: (n,) int32 ids in [0, n_seg) or -1; give `q` for np.percentile(q)
+    (method "linear") or `frac` for the k-th smallest with k = min(count, max(kmin, int(frac * count))).
+    Returns (counts (n_seg,) int32, values (n_seg,) float64; NaN where count <= min_count)."""
+    if (q is None) == (frac is None):
+        raise ValueError("give exactly one of q and frac")
+    if keys.device.type != "cuda":
+        raise _lib.DPError("segmented_select runs on the ROCm device (dp_seg_select)")
+    keys = keys.contiguous()
+    seg = seg.contiguous()
+    if keys.dtype != torch.float64 or seg.dtype != torch.int32 or keys.dim() != 1 or seg.shape != keys.shape:
+        raise ValueError("keys must be (n,) float64 and seg (n,) int32")
+    n, dev = keys.shape[0], keys.device
+    lib = _lib.load()
+    if count is not None:
+        count = count.detach().to(device=dev, dtype=torch.int32).reshape(1)
+    counts = torch.empty(n_seg, dtype=torch.int32, device=dev)
+    values = torch.empty(n_seg, dtype=torch.float64, device=dev)
+    ws = torch.empty(int(lib.dp_ground_workspace_size(n)), dtype=torch.uint8, device=dev)
+    mode, param = (_lib.DP_SEL_PERCENTILE, float(q)) if q is not None else (_lib.DP_SEL_KTH, float(frac))
+    check(lib.dp_seg_select(keys.data_ptr(), 1, seg.data_ptr(), None if count is None else count.data_ptr(), n,
+                            int(n_seg), mode, param, int(kmin), int(min_count), counts.data_ptr(), values.data_ptr(),
+                            ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream), "dp_seg_select")
+    return counts, values
+
+
+def ground_trace(points: torch.Tensor, count=None, grid_size: int = 20):
+    """The fit's ground trace on the device (`dp_ground_trace`), then read back (one synchronisation):
+    (trace (g, 4) = mean x, y, z + bin count, valid (g,) bool, info = [finite, non-finite, z_min, z_max])."""
+    g = _check_grid(grid_size)
+    lib, pts, n, count, cptr, ws, stream = _ground_args(points, count)
+    blob = torch.empty(g * 4 + 4 + (g + 1) // 2, dtype=torch.float64, device=pts.device)   # trace | info | valid (int32)
+    base = blob.data_ptr()
+    check(lib.dp_ground_trace(pts.data_ptr(), cptr, n, g, base, base + (g * 4 + 4) * 8, base + g * 32,
+                              ws.data_ptr(), ws.numel(), stream), "dp_ground_trace")
+    host = blob.cpu().numpy()
+    valid = host[g * 4 + 4:].view(np.int32)[:g] != 0
+    return host[:g * 4].reshape(g, 4).copy(), valid, host[g * 4:g * 4 + 4].copy()
+
+
+def _lowest_points(points: torch.Tensor, count=None) -> np.ndarray:
+    """The fit's fallback trace (:702-707): the max(10, int(0.05 n)) lowest-y points, in index order."""
+    lib, pts, n, count, cptr, ws, stream = _ground_args(points, count)
+    cap = min(n, max(10, int(0.05 * n)))
+    out = torch.empty(cap, 3, dtype=torch.float64, device=pts.device)
+    idx = torch.empty(cap, dtype=torch.int32, device=pts.device)
+    info = torch.empty(2, dtype=torch.float64, device=pts.device)
+    check(lib.dp_ground_lowest(pts.data_ptr(), cptr, n, out.data_ptr(), idx.data_ptr(), cap, info.data_ptr(),
+                               ws.data_ptr(), ws.numel(), stream), "dp_ground_lowest")
+    k = min(cap, int(info.cpu()[0].item()))
+    order = np.argsort(idx[:k].cpu().numpy(), kind="stable")
+    return out[:k].cpu().numpy()[order]
+
+
+def distance_percentile(points: torch.Tensor, normal, d: float, q: float, count=None) -> torch.Tensor:
+    """Device tensor [np.percentile(points . normal + d, q), points below the plane, finite points,
+    non-finite points] (`dp_ground_dist_percentile`); asynchronous."""
+    lib, pts, n, count, cptr, ws, stream = _ground_args(points, count)
+    out = torch.empty(4, dtype=torch.float64, device=pts.device)
+    plane = (ctypes.c_double * 4)(float(normal[0]), float(normal[1]), float(normal[2]), float(d))
+    check(lib.dp_ground_dist_percentile(pts.data_ptr(), cptr, n, plane, float(q), out.data_ptr(), ws.data_ptr(),
+                                        ws.numel(), stream), "dp_ground_dist_percentile")
+    return out
+
+
+def fit_trace_plane(trace: np.ndarray):
+    """Host part of the fit on the trace points ((k, 3), numpy only): (unit normal, d) before the push-down.
+
+    Least-squares plane y = a x + c z + d, refitted after dropping the trace points with residual
+    > 0.1 until nothing changes -- the deterministic limit of the reference's RANSACRegressor
+    (min_samples=10, residual_threshold=0.1, :718-725), which it reaches whenever every trace point
+    is an inlier.  Fewer than 10 trace points (RANSAC raises in the reference), fewer than 3 inliers
+    or a plane steeper than 20 degrees give the horizontal plane at the trace's median y (:754-764).
+    As in the reference, d is the intercept of the un-normalised plane (it is not divided by the
+    normal's length)."""
+    trace = np.asarray(trace, dtype=np.float64).reshape(-1, 3)
+    horizontal = (np.array([0.0, 1.0, 0.0]), -float(np.median(trace[:, 1])))
+    if len(trace) < 10:
+        return horizontal
+    X, y = trace[:, [0, 2]], trace[:, 1]
+    keep = np.ones(len(trace), dtype=bool)
+    while True:
+        if keep.sum() < 3:
+            return horizontal
+        xm, ym = X[keep].mean(axis=0), y[keep].mean()
+        coef = np.linalg.lstsq(X[keep] - xm, y[keep] - ym, rcond=None)[0]
+        icpt = ym - xm @ coef
+        new = np.abs(y - (X @ coef + icpt)) <= 0.1
+        if (new == keep).all():
+            break
+        keep = new
+    normal = np.array([-coef[0], 1.0, -coef[1]])
+    normal = normal / np.linalg.norm(normal)
+    angle = np.arccos(np.abs(normal[1])) * 180 / np.pi
+    if angle > 20:
+        return horizontal
+    return normal, -float(icpt)
+
+
+def fit_ground_plane(points: torch.Tensor, count=None, grid_size: int = 20) -> dict:
+    """The reference's `grid_based_ground_plane_fit(points, None, grid_size)` (:601-816): a model
+    dict with its keys `normal` (unit, y up), `d`, `origin`.
+
+    Device: the z-binned ground trace (or the lowest-5 % fallback when fewer than 10 bins qualify)
+    and the 0.1-percentile of the signed distances.  Host: `fit_trace_plane` on <= 32 points, then
+    the reference's push-down (d -= percentile + 0.05 when more than 0.1 % of the points lie below).
+    Two small read-backs (the trace, about 4 * grid_size + 4 doubles, then 4 doubles), each a
+    synchronisation; the fallback reads its selected points back as well.
+    Stated differences: the reference's RANSAC is stochastic, this is the deterministic limit it
+    reaches when every trace point is an inlier; `optimize_ground_plane` and the reference's random
+    50 000-point pre-sample are not built; points with a non-finite coordinate are ignored."""
+    trace, valid, info = ground_trace(points, count, grid_size)
+    if info[0] == 0:
+        raise ValueError("fit_ground_plane: no finite points")
+    tr = trace[valid, :3]
+    if len(tr) < 10:
+        tr = _lowest_points(points, count)
+    normal, d = fit_trace_plane(tr)
+    if normal[1] < 0:
+        normal, d = -normal, -d
+    pct, below, total, _ = distance_percentile(points, normal, d, 0.1, count).cpu().tolist()
+    if below > 0 and below > 0.001 * total:
+        d -= (pct + 0.05)
+    return {"normal": normal, "d": float(d), "origin": np.array([0.0, -d / normal[1] if normal[1] != 0 else 0.0, 0.0])}
+
+
+def ground_rotation(ground_model: dict) -> np.ndarray:
+    """The 15 host doubles `dp_ground_normalize` takes: unit normal, d, R (row-major), const, rotate
+    flag -- the reference's Rodrigues construction (:908-946), its |n . y| > 0.99 no-rotation branch
+    (which also skips `const`) included."""
+    normal = np.asarray(ground_model["normal"], dtype=np.float64)
+    d = float(ground_model["d"])
+    unit = normal / np.linalg.norm(normal)             # point_plane_distances (:872-873)
+    to_vec = np.array([0.0, 1.0, 0.0])
+    R, const, rotate = np.eye(3), 0.0, 0.0
+    if not np.abs(np.dot(normal, to_vec)) > 0.99:
+        from_vec = normal / np.linalg.norm(normal)
+        axis = np.cross(from_vec, to_vec)
+        axis = axis / np.linalg.norm(axis)
+        angle = np.arccos(np.clip(np.dot(from_vec, to_vec), -1.0, 1.0))
+        K = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+        R = np.eye(3) + np.sin(angle) * K + (1 - np.cos(angle)) * (K @ K)
+        const = -d / (R @ normal)[1]
+        rotate = 1.0
+    return np.concatenate([unit, [d], R.reshape(-1), [const, rotate]]).astype(np.float64)
+
+
+NORMALIZE_STATS = ("finite", "non_finite", "near_ground", "ground_level", "level_taken", "ground_points",
+                   "set_to_zero", "limited_to_minus_10cm")
+ADJUST_STATS = ("finite", "non_finite", "cells_non_empty", "cells_with_points", "cells_adjusted", "points_adjusted",
+                "reserved0", "reserved1")
+
+
+def normalize_to_ground(points: torch.Tensor, ground_model: dict, count=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`normalize_point_cloud_to_ground` (:880-981) on the device: (levelled (N, 3) float64 tensor,
+    stats (8,) float64 device tensor in `NORMALIZE_STATS` order).  Asynchronous; rows past `count`
+    are left uninitialised; points with a non-finite coordinate are copied unchanged and counted."""
+    lib, pts, n, count, cptr, ws, stream = _ground_args(points, count)
+    out = torch.empty_like(pts)
+    stats = torch.empty(8, dtype=torch.float64, device=pts.device)
+    m = ground_rotation(ground_model)
+    model = (ctypes.c_double * 15)(*m.tolist())
+    check(lib.dp_ground_normalize(pts.data_ptr(), out.data_ptr(), cptr, n, model, stats.data_ptr(), ws.data_ptr(),
+                                  ws.numel(), stream), "dp_ground_normalize")
+    return out, stats
+
+
+def ground_adjust(points: torch.Tensor, grid_size: int = 20, percentile: float = 5, count=None
+                  ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`grid_based_ground_adjustment` (:983-1118) on the device: (adjusted (N, 3) float64 tensor,
+    stats (8,) float64 device tensor in `ADJUST_STATS` order).  Asynchronous, as `normalize_to_ground`."""
+    g = _check_grid(grid_size)
+    if not 0 <= float(percentile) <= 100:
+        raise ValueError("percentile must be in [0, 100]")
+    lib, pts, n, count, cptr, ws, stream = _ground_args(points, count)
+    out = torch.empty_like(pts)
+    stats = torch.empty(8, dtype=torch.float64, device=pts.device)
+    check(lib.dp_ground_adjust(pts.data_ptr(), out.data_ptr(), cptr, n, g, float(percentile), stats.data_ptr(),
+                               ws.data_ptr(), ws.numel(), stream), "dp_ground_adjust")
+    return out, stats
+
+
+GROUND_JSON = "ground.json"
+
+
+def save_ground_plane_params(ground_model: Optional[dict], image_path: str, output_dir: Optional[str] = None
+                             ) -> Optional[str]:
+    """Write the plane as the reference does (:225-263): `ground.json` in `output_dir` (default: the
+    image's directory), keys `normal`, `d`, `origin`, `json.dump(..., indent=4)`."""
+    if ground_model is None:
+        return None
+    as_list = lambda v: v.tolist() if isinstance(v, np.ndarray) else v   # noqa: E731
+    model = {"normal": as_list(ground_model["normal"]), "d": float(ground_model["d"]),
+             "origin": as_list(ground_model["origin"])}
+    if output_dir is None:
+        output_dir = os.path.dirname(image_path)
+    os.makedirs(output_dir, exist_ok=True)
+    path = os.path.join(output_dir, GROUND_JSON)
+    with open(path, "w") as f:
+        json.dump(model, f, indent=4)
+    return path
+
+
+def load_ground_plane_params(image_path: str, input_dir: Optional[str] = None) -> Optional[dict]:
+    """Read the plane back (:265-312): `ground.json`, else the legacy `{base}_ground_plane.json`;
+    None if neither exists or the file cannot be read."""
+    if input_dir is None:
+        input_dir = os.path.dirname(image_path)
+    path = os.path.join(input_dir, GROUND_JSON)
+    if not os.path.exists(path):
+        base = os.path.splitext(os.path.basename(image_path))[0]
+        legacy = os.path.join(input_dir, f"{base}_ground_plane.json")
+        if os.path.exists(legacy):
+            path = legacy
+    if not os.path.exists(path):
+        return None
+    try:
+        with open(path) as f:
+            m = json.load(f)
+        return {"normal": np.array(m["normal"]), "d": m["d"], "origin": np.array(m["origin"]), "inliers_3d": None}
+    except Exception:   # the reference returns None on any read / parse error
+        return None
+
+
+def apply_rotation_to_plane(ground_model: Optional[dict], rotation_offset) -> Optional[dict]:
+    """Rotate the plane normal by [rx, ry, rz] degrees (R = Rz Ry Rx) and recompute d through the
+    model's origin (:314-373).  Host only."""
+    if ground_model is None:
+        return None
+    rx, ry, rz = np.radians(rotation_offset)
+    Rx = np.array([[1, 0, 0], [0, np.cos(rx), -np.sin(rx)], [0, np.sin(rx), np.cos(rx)]])
+    Ry = np.array([[np.cos(ry), 0, np.sin(ry)], [0, 1, 0], [-np.sin(ry), 0, np.cos(ry)]])
+    Rz = np.array([[np.cos(rz), -np.sin(rz), 0], [np.sin(rz), np.cos(rz), 0], [0, 0, 1]])
+    R = Rz @ Ry @ Rx
+    normal = R @ np.asarray(ground_model["normal"])
+    normal = normal / np.linalg.norm(normal)
+    out = dict(ground_model)
+    out["normal"] = normal
+    out["d"] = -np.dot(normal, ground_model["origin"])
+    return out

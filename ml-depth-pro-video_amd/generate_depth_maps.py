@@ -248,23 +248,40 @@ def plan_frames(image_paths, output_dir: str, world: int, rank: int, resume: boo
 
 def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_factor=1.0, half_precision=False,
                               colored=True, cmap="turbo", decode_workers=4, encode_workers=None, pointcloud=False,
-                              resume=False, model=None):
+                              resume=False, model=None, normalize_ground=False, ground_params_dir=None, grid_size=20,
+                              ground_percentile=5, rotation_offset=None):
     """Directory loop (reference :153-206), pipelined decode -> GPU -> encode, frame-sharded across ranks.
 
     Every rank writes its own frames' files; each frame has exactly one owner.  resume=True skips
     frames whose `{base}_depth.png` already exists (checkpoint/resume row).
     pointcloud=True also writes `{base}_points.ply` per frame: the reference's depth_to_3d
     back-projection with the frame's focal length (EXIF, or the FOV head's) and RGB colours
-    (the reference's ground-plane normalisation is out of scope).
+    (SURVEY 8f).  normalize_ground=True (implies pointcloud) levels that cloud first, as the
+    reference's img_to_normalized_pointcloud.py does per image (:1228-1287): ground plane at y = 0
+    (`PC.normalize_to_ground`), then the per-cell adjustment (`PC.ground_adjust` with grid_size /
+    ground_percentile); same point order and colours, same writer path.  Video semantics (ours): the
+    plane is read from `ground.json` in ground_params_dir (default: output_dir) if present, else
+    fitted on the first frame this run processes (`PC.fit_ground_plane`, rank 0 under torchrun, which
+    broadcasts it) and saved there; it is then reused for every frame, so a fixed camera does not get
+    a jittering floor.  rotation_offset ([rx, ry, rz] degrees, `PC.apply_rotation_to_plane`) is
+    applied to the plane in use, not to the saved file, so a re-run does not rotate twice.
     `model`: an already-built (model, transform) pair (tests); default: `_model`.
     Returns the number of frames this rank wrote.
     """
+    ground = None
+    if normalize_ground:
+        check_grid_size(grid_size)
+        pointcloud = True
+        ground = {"model": None, "dir": ground_params_dir or output_dir, "grid": int(grid_size),
+                  "pct": ground_percentile, "rot": rotation_offset, "resolved": False}
     os.makedirs(output_dir, exist_ok=True)
     image_paths = sorted(glob.glob(os.path.join(input_dir, pattern)))
     if not image_paths:
         print(f"No images found matching pattern {os.path.join(input_dir, pattern)}")
         return 0
     world, rank = _dist()
+    if ground is not None:
+        ground["world"], ground["rank"] = world, rank
     mine = plan_frames(image_paths, output_dir, world, rank, resume)
     print(f"[rank {rank}/{world}] Found {len(image_paths)} images, processing {len(mine)}")
     if model is None:
@@ -322,7 +339,7 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                     host = _image_async(depth, colored, cmap)
                     gpu_img = True
                     if pointcloud:
-                        pc = _points(depth, pred["focallength_px"], image)
+                        pc = _points(depth, pred["focallength_px"], image, ground, image_paths[k])
                     ev = torch.cuda.Event()
                     ev.record()
                 else:
@@ -348,13 +365,58 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
             print(f"[{n + 1}/{len(mine)}] Processing {base_name}")
         for f in pending:
             collect(f)
+    if ground is not None and world > 1 and not ground["resolved"]:
+        _ground_plane(ground, None, None, None)      # a rank without frames still takes part in the broadcast
     dt = time.time() - t0
     print(f"Processing complete: {successful}/{len(mine)} images successfully processed "
           f"({len(mine) / max(dt, 1e-9):.2f} frames/s on rank {rank})")
     return successful
 
 
-def _points(depth: torch.Tensor, f_px, image):
+MAX_GRID_SIZE = PC.MAX_GRID
+
+
+def check_grid_size(grid_size) -> None:
+    if not 1 <= int(grid_size) <= MAX_GRID_SIZE:
+        raise ValueError(f"--grid_size must be in [1, {MAX_GRID_SIZE}] (got {grid_size})")
+
+
+def _ground_plane(ground: dict, xyz, count, image_path):
+    """The plane every frame of this run is levelled with, resolved once per rank: rank 0 loads
+    `ground.json` or fits the frame at hand (two small read-backs) and saves it; with several ranks it
+    then broadcasts normal, d and origin through the process group -- exactly one collective per rank
+    and run, whatever the outcome (a rank without frames, or rank 0 without a plane, takes part with
+    "no plane", and every later frame of the other ranks fails on that remembered outcome without
+    another collective).  The rotation offset is applied last."""
+    if ground["resolved"]:
+        return ground["model"]
+    model = None
+    if ground["rank"] == 0:
+        model = PC.load_ground_plane_params(image_path or os.path.join(ground["dir"], "frame"), ground["dir"])
+        if model is None and xyz is not None:
+            try:
+                model = PC.fit_ground_plane(xyz, count, ground["grid"])
+                PC.save_ground_plane_params(model, image_path, ground["dir"])
+            except Exception as e:      # the other ranks must still get their broadcast
+                print(f"Ground plane fit failed: {e}")
+    if ground["world"] > 1:
+        on_gpu = dist.get_backend() == "nccl"
+        box = torch.zeros(8, dtype=torch.float64, device=(xyz.device if xyz is not None else _device()) if on_gpu
+                          else "cpu")
+        if model is not None:
+            box[:7] = torch.from_numpy(np.concatenate([model["normal"], [model["d"]], model["origin"]]))
+            box[7] = 1.0
+        dist.broadcast(box, src=0)
+        v = box.cpu().numpy()
+        model = {"normal": v[:3].copy(), "d": float(v[3]), "origin": v[4:7].copy()} if v[7] else None
+    if model is not None and ground["rot"] is not None and any(float(r) != 0.0 for r in ground["rot"]):
+        model = PC.apply_rotation_to_plane(model, ground["rot"])
+    ground["model"] = model
+    ground["resolved"] = model is not None or ground["world"] > 1   # alone, the next frame may still fit one
+    return model
+
+
+def _points(depth: torch.Tensor, f_px, image, ground=None, image_path=None):
     """Queue the frame's point cloud on the GPU (depth_to_3d, img_to_normalized_pointcloud.py:819-856),
     interleaved into PLY vertex records there, and their copy into a pinned host buffer, on the
     current stream, without a host synchronisation: the full-size record buffer + the point count
@@ -363,6 +425,14 @@ def _points(depth: torch.Tensor, f_px, image):
     rgb = image.to(depth.device, non_blocking=True) if torch.is_tensor(image) else \
         torch.from_numpy(np.ascontiguousarray(image)).to(depth.device, non_blocking=True)
     xyz, _, cols, count = PC.depth_to_points_async(depth, f_px, w, h, rgb=rgb)
+    if ground is not None:
+        # levelled cloud (--normalize_ground): queued on the same stream, still no synchronisation
+        # once the plane is known (the first frame's fit reads back a few dozen doubles)
+        plane = _ground_plane(ground, xyz, count, image_path)
+        if plane is None:
+            raise RuntimeError("no ground plane (rank 0 could neither load nor fit one)")
+        xyz, _ = PC.normalize_to_ground(xyz, plane, count)
+        xyz, _ = PC.ground_adjust(xyz, ground["grid"], ground["pct"], count)
     out = []
     for t in (PC.ply_records_async(xyz, cols), count):
         hbuf = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
@@ -388,16 +458,35 @@ def main():
     parser.add_argument("--raw", action="store_true", help="Save raw depth maps (grayscale) instead of colored ones")
     parser.add_argument("--pointcloud", action="store_true",
                         help="Also write {frame}_points.ply (depth_to_3d back-projection with RGB colours)")
+    parser.add_argument("--normalize_ground", action="store_true",
+                        help="Level {frame}_points.ply so the ground is y = 0 (implies --pointcloud): plane from "
+                             "ground.json or fitted on the first frame, then the grid-based ground adjustment")
+    parser.add_argument("--ground_params_dir", type=str, default=None,
+                        help="Directory to save/load ground plane parameters (ground.json; default: --output_dir)")
+    parser.add_argument("--rot_x", type=float, default=0.0, help="Ground plane rotation offset around X (degrees)")
+    parser.add_argument("--rot_y", type=float, default=0.0, help="Ground plane rotation offset around Y (degrees)")
+    parser.add_argument("--rot_z", type=float, default=0.0, help="Ground plane rotation offset around Z (degrees)")
+    parser.add_argument("--grid_size", type=int, default=20,
+                        help=f"Grid cells per axis for the ground adjustment (1..{MAX_GRID_SIZE}, default 20)")
+    parser.add_argument("--ground_percentile", type=int, default=5,
+                        help="Percentile of the lowest points per cell for the ground adjustment (default 5)")
     parser.add_argument("--resume", action="store_true",
                         help="Skip frames whose {frame}_depth.png already exists in --output_dir")
     parser.add_argument("--colormap", type=str, default="turbo",
                         choices=["turbo", "viridis", "plasma", "inferno", "magma", "cividis", "jet"],
                         help="Colormap for depth visualization")
     args = parser.parse_args()
+    if not 1 <= args.grid_size <= MAX_GRID_SIZE:
+        parser.error(f"--grid_size must be in [1, {MAX_GRID_SIZE}] (got {args.grid_size})")
+    if not 0 <= args.ground_percentile <= 100:
+        parser.error("--ground_percentile must be in [0, 100]")
     batch_generate_depth_maps(input_dir=args.input_dir, output_dir=args.output_dir, pattern=args.pattern,
                               downscale_factor=args.downscale_factor, half_precision=args.half_precision,
                               colored=not args.raw, cmap=args.colormap, pointcloud=args.pointcloud,
-                              resume=args.resume)
+                              resume=args.resume, normalize_ground=args.normalize_ground,
+                              ground_params_dir=args.ground_params_dir, grid_size=args.grid_size,
+                              ground_percentile=args.ground_percentile,
+                              rotation_offset=[args.rot_x, args.rot_y, args.rot_z])
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()

@@ -36,6 +36,8 @@ def main():
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--size", default="1536x1536", help="WxH of the input frames")
     ap.add_argument("--pointcloud", action="store_true")
+    ap.add_argument("--normalize-ground", action="store_true",
+                    help="level the point clouds (--normalize_ground of the loop; implies --pointcloud)")
     ap.add_argument("--raw", action="store_true")
     ap.add_argument("--workers", type=int, default=None,
                     help="decode and encode threads each (default: the loop's own defaults)")
@@ -122,7 +124,11 @@ def main():
     m, transform = model
     torch.cuda.synchronize()
     t_setup = time.time() - t
+    if args.normalize_ground:
+        args.pointcloud = True
     kw = dict(colored=not args.raw, pointcloud=args.pointcloud, model=model)
+    if args.normalize_ground:
+        kw["normalize_ground"] = True
     if args.workers:
         kw.update(decode_workers=args.workers, encode_workers=args.workers)
     import inspect
@@ -207,7 +213,8 @@ def main():
         t_ply = time.time() - t
     out = {
         "what": "generate_depth_maps.batch_generate_depth_maps end to end, 1 GPU",
-        "frames": args.frames, "size": [W, H], "pointcloud": args.pointcloud, "raw": args.raw,
+        "frames": args.frames, "size": [W, H], "pointcloud": args.pointcloud, "normalize_ground": args.normalize_ground,
+        "raw": args.raw,
         "ply_records": "host (numpy)" if args.ply_host else "GPU",
         "png_writer": "bytes copies" if args.png_copy else "zero-copy parts",
         "switch_ms": args.switch_ms,

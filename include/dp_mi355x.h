@@ -62,7 +62,22 @@ int dp_abi_version(void);
  *                           64-channel block are consecutive: shifted input re-reads hit L2).
  * B operand: packed weights B[n][k] row-major (ldb), i.e. W for a Linear,
  *            [Cout][Cin/64][ky][kx][64] for a conv, [(dy,dx,Cout)][Cin] for a k2s2 deconv.
- * Requirements: K % 64 == 0, N % 4 == 0, lda/ldb % 8 == 0, in_c % 64 == 0 (conv).
+ * Requirements: K % 64 == 0, N % 4 == 0 (DP_ERR_SHAPE), lda/ldb % 8 == 0 (DP_ERR_ALIGN),
+ *   in_c % 64 == 0 (conv).  Any M >= 1; any conv geometry with M = batch*out_h*out_w.
+ * Alignment of the epilogue operands (DP_ERR_ALIGN; elements; a rule applies only where the operand
+ *   is used): every epilogue reads and writes 4 consecutive columns at row*ld + n in one 8- or
+ *   16-byte access, so on every engine
+ *     ldc % 4 == 0 (16-bit and fp32 C; no ldc with the fused head / DP_STORE_HEAD_PS),
+ *     ldr1 % 4 == 0, ldr2 % 4 == 0, ldpos % 4 == 0, dc_cout % 4 == 0 (DP_ERR_SHAPE),
+ *   and the pointers C, R1, R2, pos, bias, gamma, head_w aligned to 4 of their elements (A, B: 8).
+ *   The 8-column engines (every DP_TILE_* from DP_TILE_BIG_256x256 = 4 up, below) work on 8
+ *   consecutive columns (16-byte accesses to 16-bit rows, one deconv sub-pixel per 8 columns):
+ *     N % 8 == 0 and, with DP_STORE_DECONV2X2, dc_cout % 8 == 0      (DP_ERR_SHAPE), then
+ *     ldr1 % 8 == 0, ldr2 % 8 == 0, and ldc % 8 == 0 for a 16-bit C  (DP_ERR_ALIGN; those
+ *     pointers aligned to 8 elements)
+ *   (an fp32 C and pos keep the % 4 rule).  Under DP_TILE_AUTO a problem that does not meet the
+ *   8-column rules runs on the 4-column engines (DP_TILE_128x128 for N > 64); with a hint for an
+ *   8-column engine it is the error named above.
  *
  * Epilogue, per element, in this order:
  *   v = acc (+ bias[n]) ; act(v) ; (* gamma[n]) ; (+ pos[(m % pos_group) + pos_off][n])
@@ -168,7 +183,38 @@ enum { DP_TILE_AUTO = 0, DP_TILE_128x128 = 1, DP_TILE_256x64 = 2, DP_TILE_256x32
        DP_TILE_PBIG_256x256 = 16, DP_TILE_DUAL_256x128 = 17,
        DP_TILE_P8PH_256x256 = 18, DP_TILE_8PH_320x256 = 19, DP_TILE_CV3_256x256 = 20,
        DP_TILE_SPLITK_256x256 = 21, DP_TILE_CV3_192x256 = 22, DP_TILE_CV3_384x128 = 23 };
-/* DP_TILE_P8PH_256x256: persistent 8-phase engine (min(tiles, CUs) workgroups, each a stream of
+/* What a tile hint accepts.  DP_TILE_AUTO never fails for a problem the contract above allows.  The
+   checks run in this order; the first that fails gives the return code:
+   1. the general argument checks (above), for every hint;
+   2. the fused 1x1 head (head_w with DP_STORE_ROWS) always runs on DP_TILE_256x32 and
+      DP_STORE_HEAD_PS on a 128-column conv engine (the hint is kept only if it is
+      DP_TILE_BIG_256x128, DP_TILE_CV3_256x256 or DP_TILE_CV3_384x128): other hints are ignored,
+      not rejected;
+   3. hints 1 - 3 (DP_TILE_128x128, 256x64, 256x32: the 4-column engines) take everything else
+      except head_corr (DP_ERR_ARG);
+   4. every hint >= DP_TILE_BIG_256x256: the 8-column rules (DP_ERR_SHAPE, then DP_ERR_ALIGN);
+   5. then per engine (DP_ERR_ARG unless noted):
+      - DP_TILE_BIG_* / DEEP* / DUAL / 8PH_256x256 (4 - 11, 13, 14, 17): nothing more (dense and
+        conv A, every epilogue operand and store mode); head_corr with DP_STORE_ROWS only on
+        DP_TILE_BIG_512x128 (and the CV3 engines);
+      - DP_TILE_STREAMK_256x256: a workspace, N % 256 == 0;
+      - DP_TILE_SPLITK_256x256: a workspace, N % 256 == 0, DP_STORE_ROWS without row groups; then
+        DP_ERR_SHAPE unless min(CUs / tiles, (K / 64) / 2, (workspace_bytes - 4096) / (4 M N), 32)
+        >= 2, tiles = ceil(M / 256) * (N / 256);
+      - DP_TILE_PBIG_320x256 / PBIG_256x256: N % 256 == 0, DP_STORE_ROWS (row groups allowed), the
+        byte extent of C below 2^32 - 256, M * lda and N * ldb below 2^31;
+      - DP_TILE_P8PH_256x256: dense A, N % 256 == 0, K >= 128, a 16-bit C, no R1 / R2 / pos /
+        accumulate / row groups, the same extent limits, and DP_STORE_ROWS, or DP_STORE_DECONV2X2
+        without relu_a / act / gamma and with dc_w >= 8;
+      - DP_TILE_8PH_320x256: dense A, no relu_a, N % 256 == 0, DP_STORE_ROWS, no R1 / R2 / pos /
+        row groups, M * lda and N * ldb below 2^31, and either a 16-bit C (not accumulated) or an
+        fp32 C accumulated into without activation;
+      - DP_TILE_CV3_*: a stride-1 pad-1 3x3 conv over square maps (in = out side S, S % 16 == 0;
+        S % 48 == 0 for 192x256 and 384x128), no gamma / pos / accumulate / row groups / GELU,
+        M * in_c < 2^30; a 16-bit C with N % 256 == 0 (N % 128 == 0 with head_corr, then no
+        R1 / R2), or DP_STORE_HEAD_PS; 192x256 without head_corr; 384x128 only with head_corr or
+        DP_STORE_HEAD_PS at N == 128.
+   DP_TILE_P8PH_256x256: persistent 8-phase engine (min(tiles, CUs) workgroups, each a stream of
    K steps over its tiles; dense A, N % 256 == 0, K >= 128, 16-bit C without per-row operands);
    the auto choice for the ViT fc1.  DP_TILE_8PH_320x256: 8-phase 320 x 256 engine (dense A, no
    ReLU prologue, N % 256 == 0; 16-bit C without per-row operands, or an fp32 C accumulated into

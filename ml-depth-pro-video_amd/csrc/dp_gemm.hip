@@ -78,6 +78,11 @@ int gemm_plan(const dp_gemm_args* a, GemmP& p, int& tile) {
   if (a->M <= 0 || a->N <= 0 || a->K <= 0) return DP_ERR_SHAPE;
   if (a->K % BK != 0 || a->N % 4 != 0) return DP_ERR_SHAPE;
   if (a->ldb % 8 != 0 || (a->a_mode == DP_A_DENSE && a->lda % 8 != 0)) return DP_ERR_ALIGN;
+  // every epilogue reads / writes 4 consecutive columns at row * ld + n as one 8- or 16-byte access
+  // (C is a plain [M] vector for the fused head and a pixel map for DP_STORE_HEAD_PS: no ldc there)
+  if ((!a->head_w && a->store_mode != DP_STORE_HEAD_PS && a->ldc % 4 != 0) || (a->R1 && a->ldr1 % 4 != 0) ||
+      (a->R2 && a->ldr2 % 4 != 0) || (a->pos && a->ldpos % 4 != 0))
+    return DP_ERR_ALIGN;
   if (!a->A || !a->B || (!a->C && !a->ln_xl)) return DP_ERR_ARG;   // split-residual producer: C optional
   if (a->dtype != DP_BF16 && a->dtype != DP_F16) return DP_ERR_DTYPE;
   if (a->c_dtype != DP_BF16 && a->c_dtype != DP_F16 && a->c_dtype != DP_F32) return DP_ERR_DTYPE;
@@ -150,12 +155,24 @@ int gemm_plan(const dp_gemm_args* a, GemmP& p, int& tile) {
     if (a->N > 32 || a->store_mode != DP_STORE_ROWS) return DP_ERR_SHAPE;
     tile = DP_TILE_256x32;
   }
+  // The engines from DP_TILE_BIG_256x256 up run their epilogues on 8 consecutive columns (16-byte
+  // accesses to the 16-bit C / R1 / R2), and take the deconv parity n / dc_cout once per 8 columns:
+  // N % 8 == 0, dc_cout % 8 == 0 (a chunk must not straddle two sub-pixels), ldr1 / ldr2 % 8 == 0
+  // and, for a 16-bit C, ldc % 8 == 0.  What does not meet it runs on the 4-column engines
+  // (128 x 128 under DP_TILE_AUTO); a hint for an 8-column engine is an error.
+  const bool col8_shape = a->N % 8 == 0 && !(a->store_mode == DP_STORE_DECONV2X2 && a->dc_cout % 8 != 0);
+  const bool col8_align = !(a->c_dtype != DP_F32 && a->ldc % 8 != 0) && !(a->R1 && a->ldr1 % 8 != 0) &&
+                          !(a->R2 && a->ldr2 % 8 != 0);
+  if (tile >= DP_TILE_BIG_256x256) {
+    if (!col8_shape) return DP_ERR_SHAPE;
+    if (!col8_align) return DP_ERR_ALIGN;
+  }
   const long long tiles256 = (long long)((a->M + 255) / 256) * (a->N / 256);
   if (tile == DP_TILE_STREAMK_256x256 && (!ws_ok || a->N % 256 != 0)) return DP_ERR_ARG;
   if (tile == DP_TILE_AUTO) {
     if (a->N <= 32) tile = DP_TILE_256x32;
     else if (a->N <= 64) tile = DP_TILE_256x64;
-    else if (a->N % 8 != 0) tile = DP_TILE_128x128;
+    else if (!col8_shape || !col8_align) tile = DP_TILE_128x128;
     else if (a->N == 128 && a->M >= 512 * 256) {   // N = 128 convs at 768^2: the head.0 conv
       // the patch-conv engine for the stride-1 square ones (the composed out_conv∘head.0), on
       // 24 x 16-pixel tiles where the side allows (48 MFMAs per wave and K step instead of 32: 381 ->
@@ -281,7 +298,8 @@ int gemm_plan(const dp_gemm_args* a, GemmP& p, int& tile) {
   // Debug 1 << 23: off.
   const bool dcv = a->store_mode == DP_STORE_DECONV2X2 && !a->relu_a && !a->gamma && a->act == DP_ACT_NONE &&
                    a->dc_w >= 8;   // (the persistent engine's deconv store steps its rows 8 pixels at a time)
-  if (a->tile == DP_TILE_AUTO && dcv && !(dbg & (1 << 23)) && tiles256 >= 128) tile = DP_TILE_P8PH_256x256;
+  if (a->tile == DP_TILE_AUTO && dcv && col8_shape && col8_align && !(dbg & (1 << 23)) && tiles256 >= 128)
+    tile = DP_TILE_P8PH_256x256;
   if (tile == DP_TILE_P8PH_256x256 || (a->tile == DP_TILE_AUTO && tile == DP_TILE_8PH_256x256 && !(dbg & (1 << 22)))) {
     const bool ok = a->a_mode == DP_A_DENSE && a->N % 256 == 0 && a->K >= 128 && a->c_dtype != DP_F32 &&
                     ((a->store_mode == DP_STORE_ROWS && c_bytes) || (dcv && dcv_bytes)) && !a->R1 && !a->R2 && !a->pos && !a->accumulate &&
@@ -317,7 +335,7 @@ int gemm_plan(const dp_gemm_args* a, GemmP& p, int& tile) {
       a->stride == 1 && a->pad == 1 && a->in_h == a->in_w && a->out_h == a->in_h && a->out_w == a->in_w &&
       a->in_w % 16 == 0 && a->in_c % 64 == 0 && a->N % 256 == 0 && a->store_mode == DP_STORE_ROWS &&
       !a->row_group && !a->head_w && !a->head_corr && (long long)a->M * a->in_c < (1LL << 30) && off32 &&
-      a->c_dtype != DP_F32 && !a->gamma && !a->pos && !a->accumulate && a->act != DP_ACT_GELU &&
+      a->c_dtype != DP_F32 && !a->gamma && !a->pos && !a->accumulate && a->act != DP_ACT_GELU && col8_align &&
       (long long)(a->M / 256) * (a->N / 256) >= 4LL * num_cus())   // many rounds (the 768^2 maps; 384^2: 201 vs 185 us)
     tile = DP_TILE_CV3_256x256;
   // ... and on 12 x 16-pixel tiles where those make whole rounds of workgroups and 16 x 16 ones do not
@@ -328,7 +346,7 @@ int gemm_plan(const dp_gemm_args* a, GemmP& p, int& tile) {
            a->out_h == a->in_h && a->out_w == a->in_w && a->in_w % 16 == 0 && a->in_w % 12 == 0 &&
            a->in_c % 64 == 0 && a->N % 256 == 0 && a->store_mode == DP_STORE_ROWS && !a->row_group && !a->head_w &&
            !a->head_corr && (long long)a->M * a->in_c < (1LL << 30) && off32 && a->c_dtype != DP_F32 && !a->gamma &&
-           !a->pos && !a->accumulate && a->act != DP_ACT_GELU) {
+           !a->pos && !a->accumulate && a->act != DP_ACT_GELU && col8_align) {
     const long long t12 = (long long)(a->M / ((long long)a->in_w * a->in_w)) * (a->in_w / 12) * (a->in_w / 16) * (a->N / 256);
     const long long ncu = num_cus();
     if (t12 >= 2 * ncu && t12 % ncu == 0 && ((long long)(a->M / 256) * (a->N / 256)) % ncu != 0) tile = DP_TILE_CV3_192x256;
@@ -337,7 +355,23 @@ int gemm_plan(const dp_gemm_args* a, GemmP& p, int& tile) {
     // same box, profiles/r05z_cv3_192/)
     else if (t12 <= ncu && 2 * t12 >= ncu) tile = DP_TILE_CV3_192x256;
   }
-  if (tile >= DP_TILE_BIG_256x256 && a->N % 8 != 0) return DP_ERR_SHAPE;  // 8-column epilogue chunks
+  if (tile >= DP_TILE_BIG_256x256 && !col8_shape) return DP_ERR_SHAPE;  // 8-column epilogue chunks
+  if (tile >= DP_TILE_BIG_256x256 && !col8_align) return DP_ERR_ALIGN;
+  // the patch-conv engine's own conditions (launch_cv3 checks them again): a hint it cannot serve
+  if (tile == DP_TILE_CV3_256x256 || tile == DP_TILE_CV3_192x256 || tile == DP_TILE_CV3_384x128) {
+    const int th = tile == DP_TILE_CV3_192x256 ? 12 : tile == DP_TILE_CV3_384x128 ? 24 : 16, S = a->out_w;
+    const bool hps = a->store_mode == DP_STORE_HEAD_PS, bc = a->store_mode == DP_STORE_ROWS && a->head_corr;
+    if (a->a_mode != DP_A_CONV || a->k_h != 3 || a->k_w != 3 || a->stride != 1 || a->pad != 1 || a->in_h != S ||
+        a->in_w != S || a->out_h != S || S % 16 != 0 || S % th != 0 || a->row_group || (a->head_w && !hps) || a->gamma ||
+        a->pos || a->accumulate || (a->act != DP_ACT_NONE && a->act != DP_ACT_RELU) ||
+        (long long)a->M * a->in_c >= (1LL << 30) || (long long)a->N * a->ldb >= (1LL << 31))
+      return DP_ERR_ARG;
+    if (!hps && a->store_mode != DP_STORE_ROWS) return DP_ERR_ARG;
+    if (bc && (a->c_dtype == DP_F32 || a->R1 || a->R2 || a->N % 128 != 0)) return DP_ERR_ARG;
+    if (!hps && !bc && (a->c_dtype == DP_F32 || a->N % 256 != 0)) return DP_ERR_ARG;
+    if (th == 12 && (hps || bc)) return DP_ERR_ARG;
+    if (th == 24 && !((hps || bc) && a->N == 128)) return DP_ERR_ARG;
+  }
   // the border-corrected composed conv exists in the 512 x 128 conv engine only
   if (a->store_mode == DP_STORE_ROWS && a->head_corr && tile != DP_TILE_BIG_512x128 && tile != DP_TILE_CV3_256x256 &&
       tile != DP_TILE_CV3_384x128)

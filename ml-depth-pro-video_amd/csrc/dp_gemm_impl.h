@@ -3251,7 +3251,8 @@ int launch_big(const GemmP& p0, bool conv, hipStream_t s) {
   dim3 grid(p.tiles_n * p.tiles_m);
   // the load-free epilogue for launches without per-row operands (needs_rowld), on the BK = 64
   // engines the planner picks; debug 1 << 20: always the general one (A/B)
-  const int ea = BKT == 64 ? fast_epi_act(p) : -1;
+  int ea = BKT == 64 ? fast_epi_act(p) : -1;
+  if (ea >= EPI_ACC && p.N % BN != 0) ea = -1;   // epilogue_acc32 has no column predicate: whole column tiles only
   if (p.groups > 1) {
     // grouped launches (the side encoders' dense GEMMs) exist for the 256 x 128 / 128 x 128 dense engines
     if constexpr ((BM == 256 || BM == 128) && BN == 128 && BKT == 64 && NS == 3 && PIPE) {
@@ -3301,7 +3302,8 @@ int launch_dual(const GemmP& p0, bool conv, hipStream_t s) {
   else if (conv)
     hipLaunchKernelGGL((gemm_big_kernel<K_, 256, 128, 32, 3, false, true, false, 4>), grid, dim3(256), 0, s, p);
   else {
-    const int ea = fast_epi_act(p);
+    int ea = fast_epi_act(p);
+    if (ea >= EPI_ACC && p.N % 128 != 0) ea = -1;   // (epilogue_acc32: whole column tiles only)
     if (p.relu_a)
       hipLaunchKernelGGL((gemm_big_kernel<K_, 256, 128, 32, 3, false, false, true, 4>), grid, dim3(256), 0, s, p);
     else if (ea == DP_ACT_NONE)

@@ -164,6 +164,81 @@ def test_gemm_plan_tile_choice():
         lib.dp_gemm_debug_flags(0)
 
 
+def test_gemm_epilogue_alignment_and_column_chunk_rules():
+    """dp_mi355x.h, 'Alignment of the epilogue operands' (host only, null stream, no launch): ldc / ldr1 /
+    ldr2 / ldpos % 4 on every engine; N % 8, dc_cout % 8 (DP_ERR_SHAPE) and ldr1 / ldr2 / 16-bit ldc % 8
+    (DP_ERR_ALIGN) for a hint from DP_TILE_BIG_256x256 up, while DP_TILE_AUTO takes the 4-column
+    128 x 128 engine instead of failing."""
+    lib = _lib.load()
+    t, g = ctypes.c_int32(), ctypes.c_int32()
+    SHAPE, ALIGN = 1001, 1002
+    BIG = (_lib.DP_TILE_BIG_256x256, _lib.DP_TILE_BIG_256x128, _lib.DP_TILE_8PH_256x256, _lib.DP_TILE_BIG_320x256,
+           _lib.DP_TILE_BIG_512x128, _lib.DP_TILE_DUAL_256x128, _lib.DP_TILE_DEEP_256x128)
+
+    def args(M=300, N=136, K=128, **kw):
+        a = _lib.GemmArgs()
+        a.M, a.N, a.K = M, N, K
+        a.A = a.B = a.C = 256
+        a.lda, a.ldb, a.ldc = K, K, N
+        a.dtype = a.c_dtype = _lib.DP_BF16
+        for k, v in kw.items():
+            setattr(a, k, v)
+        return a
+
+    def plan(**kw):
+        rc = lib.dp_gemm_plan(ctypes.byref(args(**kw)), ctypes.byref(t), ctypes.byref(g))
+        return rc, t.value
+
+    # % 4 on every engine, for the operands in use only; dp_gemm itself reports the same before any launch
+    for tile in (0, _lib.DP_TILE_128x128, _lib.DP_TILE_256x64, _lib.DP_TILE_BIG_256x128):
+        assert plan(tile=tile)[0] == 0
+        assert plan(tile=tile, ldc=138)[0] == ALIGN
+        assert plan(tile=tile, R1=256, ldr1=138)[0] == ALIGN
+        assert plan(tile=tile, R2=256, ldr2=142)[0] == ALIGN
+        assert plan(tile=tile, pos=256, pos_group=7, ldpos=138)[0] == ALIGN
+        assert plan(tile=tile, ldr1=138, ldr2=3, ldpos=1)[0] == 0            # no R1 / R2 / pos: not looked at
+        assert lib.dp_gemm(ctypes.byref(args(tile=tile, ldc=138)), None) == ALIGN
+    assert plan(N=32, head_w=256, c_dtype=_lib.DP_F32, ldc=1)[0] == 0       # the fused head's C is a vector
+    # % 8 for the 8-column engines: 16-bit C, R1, R2 (an fp32 C and pos keep % 4)
+    for tile in BIG:
+        assert plan(tile=tile)[:2] == (0, tile)
+        assert plan(tile=tile, ldc=140)[0] == ALIGN
+        assert plan(tile=tile, ldc=140, c_dtype=_lib.DP_F32)[0] == 0
+        assert plan(tile=tile, R1=256, ldr1=140)[0] == ALIGN
+        assert plan(tile=tile, R2=256, ldr2=140)[0] == ALIGN
+        assert plan(tile=tile, R1=256, ldr1=144, R2=256, ldr2=152, pos=256, pos_group=7, ldpos=140, ldc=144)[0] == 0
+        assert plan(tile=tile, N=132, ldc=136)[0] == SHAPE                  # N % 8
+    # ... which DP_TILE_AUTO serves on the 4-column engine
+    assert plan()[1] == _lib.DP_TILE_BIG_256x128
+    for kw in (dict(ldc=140), dict(R1=256, ldr1=140), dict(R2=256, ldr2=140), dict(N=132)):
+        assert plan(**kw) == (0, _lib.DP_TILE_128x128), kw
+    assert plan(ldc=140, c_dtype=_lib.DP_F32)[1] == _lib.DP_TILE_BIG_256x128
+
+    # the 2x2 deconv store: one sub-pixel per column chunk -- dc_cout % 4 always, % 8 on the 8-column engines
+    def deconv(cout, S=16, **kw):
+        kw.setdefault("ldc", cout)
+        kw.setdefault("K", 64)
+        return plan(M=S * S, N=4 * cout, store_mode=_lib.DP_STORE_DECONV2X2, dc_h=S, dc_w=S, dc_cout=cout, **kw)
+    assert deconv(18, ldc=24)[0] == SHAPE
+    assert deconv(20) == (0, _lib.DP_TILE_128x128)                           # N = 80: a chunk of 8 would straddle
+    assert deconv(20, c_dtype=_lib.DP_F32) == (0, _lib.DP_TILE_128x128)
+    assert deconv(24)[1] == _lib.DP_TILE_BIG_256x128
+    ws = dict(workspace=256, workspace_bytes=lib.dp_gemm_workspace_size())
+    for tile in BIG + (_lib.DP_TILE_STREAMK_256x256, _lib.DP_TILE_P8PH_256x256):
+        assert deconv(20, tile=tile, **ws)[0] == SHAPE, tile
+        assert deconv(20, tile=tile, c_dtype=_lib.DP_F32, **ws)[0] == SHAPE, tile
+    assert deconv(24, tile=_lib.DP_TILE_BIG_256x128)[0] == 0
+    assert deconv(20, tile=_lib.DP_TILE_128x128)[0] == 0
+    # the model's own deconvs plan exactly as before (cout 256 / 512 / 1024: test_gemm_plan_tile_choice)
+    assert deconv(256, S=384, K=256, dtype=_lib.DP_F16, c_dtype=_lib.DP_F16, bias=256, **ws) == \
+        (0, _lib.DP_TILE_P8PH_256x256)
+    # a patch-conv hint the engine cannot serve is refused by the plan, not at launch
+    for tile in (_lib.DP_TILE_CV3_256x256, _lib.DP_TILE_CV3_192x256, _lib.DP_TILE_CV3_384x128):
+        assert plan(N=256, tile=tile)[0] == 1000                              # dense A
+        assert plan(M=40 * 40, N=256, K=576, tile=tile, a_mode=_lib.DP_A_CONV, in_h=40, in_w=40, in_c=64, k_h=3,
+                    k_w=3, stride=1, pad=1, out_h=40, out_w=40)[0] == 1000    # side % 16
+
+
 def test_empty_inputs_are_refused_before_launch():
     """Zero-size inputs (no rows / images / pixels) return DP_ERR_SHAPE (DP_ERR_ARG for an empty
     group list) from every entry point that takes a size, before any launch (no GPU here: a launch

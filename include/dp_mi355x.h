@@ -41,7 +41,7 @@ enum { DP_A_DENSE = 0, DP_A_CONV = 1 };
 enum { DP_STORE_ROWS = 0, DP_STORE_DECONV2X2 = 1, DP_STORE_HEAD_PS = 2 };
 
 /* ABI version of this header; the Python loader refuses a mismatching .so. */
-#define DP_ABI_VERSION 15
+#define DP_ABI_VERSION 16
 int dp_abi_version(void);
 
 /*
@@ -565,6 +565,102 @@ int dp_ground_normalize(const double* points, double* points_out, const int32_t*
 int dp_ground_adjust(const double* points, double* points_out, const int32_t* n_dev, int32_t n_max,
                      int32_t grid_size, double percentile, double* stats_out, void* workspace,
                      int64_t workspace_bytes, dp_stream_t stream);
+
+/*
+ * ---- Cleaned point clouds (ABI 16, csrc/dp_clean.hip) --------------------------------------------
+ * The second stage of the reference's 3-D pipeline (pointcloud_pipeline.py, process_single_frame
+ * step 2): remove_stray_points then clean_shadows (pointcloud_cleaner.py:142-207, :209-309), on a
+ * stable device radix sort of (key, index) pairs, plus the order-preserving compaction between and
+ * after them.  The ground section's conventions hold throughout: fp64 points [n_max][3], n_dev a
+ * device int32 (NULL: n_max; clamped to [0, n_max]), n_max = 0 and *n_dev = 0 valid, everything on
+ * the caller's stream with no synchronisation and no host read-back, each fp64 product and sum
+ * rounded on its own (no FMA), argument errors returned as DP_ERR_* before any launch.
+ *   workspace  >= dp_clean_workspace_size(n_max) bytes of device memory, 8-byte aligned, owned by
+ *              the call until the stream has passed it (content need not be initialised).  About
+ *              48 bytes per point + 1 KiB per 4096 points.
+ *   keep_out   uint8 [n_max]: 1 = keep, 0 = remove, in the points' own order; entries at or beyond
+ *              the live count are not written.
+ * A "finite point" has three finite coordinates.
+ */
+int64_t dp_clean_workspace_size(int64_t n_max);
+
+/*
+ * dp_sort_pairs: stable ascending sort of the first *n_dev (keys[i], values[i]) pairs by the key
+ * bits [bit_lo, bit_hi) (0 <= bit_lo <= bit_hi <= 64; bits outside the range are ignored, pairs
+ * equal in the range keep their input order).  Least-significant-digit radix sort, 8 bits per pass;
+ * only the passes whose digit overlaps [bit_lo, bit_hi) run (a partial digit is masked), so the
+ * number of launches depends on bit_lo and bit_hi alone.  A pass is three kernels: per-workgroup
+ * digit histogram, scan of the [256][workgroups] table, scatter with in-tile ranks in input order
+ * (64-lane ballot groups + per-wave counts in LDS); no kernel waits for another workgroup.  Passes
+ * ping-pong between the caller's arrays and the workspace; the RESULT IS ALWAYS IN keys / values
+ * (an odd number of passes ends with a copy back).  Elements at or beyond *n_dev are neither read
+ * nor written.  fp64 keys are sorted through the order-preserving map of dp_seg_select (sign flip,
+ * -0.0 folded onto +0.0), which the stages below apply themselves.
+ */
+int dp_sort_pairs(uint64_t* keys, uint32_t* values, const int32_t* n_dev, int32_t n_max, int32_t bit_lo,
+                  int32_t bit_hi, void* workspace, int64_t workspace_bytes, dp_stream_t stream);
+
+/*
+ * dp_clean_stray: remove_stray_points(pcd, nb_points, radius).  Point j is kept iff the number of
+ * live finite points i, j itself included, with (dx*dx + dy*dy) + dz*dz < radius*radius (strict,
+ * every operation rounded in fp64) is >= nb_points.  This restates Open3D's
+ * KDTreeFlann.search_radius_vector_3d (nanoflann's radius result set admits dist < radius^2);
+ * Open3D itself was not available to check against, so this sentence is the specification.
+ * A point with a non-finite coordinate has no neighbours and is removed (ours; the reference is
+ * undefined there).
+ * Method: cells of edge radius * (1 + 2^-20), 21 bits per axis packed (x, y, z) with z lowest,
+ * dp_sort_pairs on (cell, index), then each point scans the 9 (x, y) cell rows around it -- a row's
+ * three z-adjacent cells are one key range -- testing the original coordinates, and stops as soon
+ * as the count reaches nb_points.  The cells only select candidates (see the argument in the source).
+ *   stats_out  fp64 [8]: finite points, non-finite points, kept, removed, error flag, 0, 0, 0
+ * Error flag (device side): an axis would need more than 2^21 - 2 cells ((max - min) / edge).  Then
+ * NO point is removed (keep_out all 1, kept = live count) rather than use a wrong neighbourhood.
+ * radius not finite or <= 0, or nb_points < 1: DP_ERR_SHAPE.
+ */
+int dp_clean_stray(const double* points, const int32_t* n_dev, int32_t n_max, double radius, int32_t nb_points,
+                   uint8_t* keep_out, double* stats_out, void* workspace, int64_t workspace_bytes,
+                   dp_stream_t stream);
+
+/*
+ * dp_clean_shadows: clean_shadows(pcd, height_threshold, max_angle, min_points).
+ *   x / z min and max over the live finite points (n of them);
+ *   density = n / ((x_max - x_min) * (z_max - z_min)); v = 1.0 / sqrt(density / 10);
+ *   cell = v if v > 0.05 else 0.05 (Python's max(0.05, v): zero area or a NaN give 0.05) -- all in a
+ *   one-thread kernel, nothing is read back;
+ *   x_bins = np.arange(x_min, x_max + cell, cell): ceil(((x_max + cell) - x_min) / cell) edges, filled
+ *   as numpy fills them: e[0] = x_min, e[1] = x_min + cell, e[i] = x_min + i * (e[1] - e[0]);
+ *   xi = np.digitize(x, x_bins) - 1 = the last i with e[i] <= x (found on the edges themselves, not
+ *   from the quotient); the same for z; column = xi * len(z_bins) + zi.
+ * A column with count >= min_points, count >= 3 and y_max - y_min > height_threshold is tested: its
+ * points ordered by y, TIES IN INDEX ORDER (stated difference: the reference's np.argsort is
+ * unstable for columns of more than 16 points), consecutive differences v,
+ * a = arccos(clip(v_y / sqrt((v_x^2 + v_y^2) + v_z^2), -1, 1)) * 180 / pi, and the column is removed
+ * iff np.median(a) < max_angle.  A zero-length v gives NaN and a NaN median: the column is kept, as
+ * numpy does.  Order: dp_sort_pairs on the y key (64 bits), then on the column id (32 bits,
+ * stable).  The median is decided without a second sort: with m angles, c of them below the limit,
+ * odd m removes iff c >= (m + 1) / 2; even m removes if c > m / 2, keeps if c < m / 2, and for
+ * c == m / 2 tests (largest angle below + smallest angle not below) / 2 < max_angle.  Per-column
+ * values are reductions over the sorted run onto its head position (no dense table of columns).
+ * A non-finite point is in no column, is kept and is counted.
+ *   stats_out  fp64 [8]: finite points, non-finite points, columns occupied, columns tested,
+ *              columns removed, points removed, cell size, error flag
+ * Error flag (device side): len(x_bins) * len(z_bins) >= 2^31 (or not finite, or edges that do not
+ * grow in fp64).  Then every point is kept.  min_points < 1 or a NaN threshold: DP_ERR_SHAPE.
+ */
+int dp_clean_shadows(const double* points, const int32_t* n_dev, int32_t n_max, double height_threshold,
+                     double max_angle, int32_t min_points, uint8_t* keep_out, double* stats_out, void* workspace,
+                     int64_t workspace_bytes, dp_stream_t stream);
+
+/*
+ * dp_compact_points: the first *n_out_dev rows of points_out (and colors_out, uint8 [n_max][3], if
+ * colors != NULL) are the live rows with keep[i] != 0, in their original order; *n_out_dev (device
+ * int32) is their number, so the next stage can take it as its n_dev.  Rows at or beyond that
+ * count are not written.  Outputs must not alias inputs.  Workgroup counts, one scan of them, an
+ * order-preserving scatter; no look-back.
+ */
+int dp_compact_points(const double* points, const uint8_t* colors, const uint8_t* keep, const int32_t* n_dev,
+                      int32_t n_max, double* points_out, uint8_t* colors_out, int32_t* n_out_dev, void* workspace,
+                      int64_t workspace_bytes, dp_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,10 @@ Ground normalisation (the rest of the reference's first 3-D stage, same file): `
 (:225-312) and `apply_rotation_to_plane` (:314-373).  All per-point work and every percentile run
 in csrc/dp_ground.hip (segmented radix selection, fp64); the host only sees the <= 32 trace points.
 Not built: `optimize_ground_plane` (scipy) and the 50 000-point random pre-sample in front of it.
+
+Cleaning (the reference pipeline's next step, `pointcloud_cleaner.py:142-309`): `remove_stray_points`,
+`clean_shadows` and `clean_pointcloud` (one after the other), on the stable device radix sort
+`sort_pairs` and an order-preserving compaction -- csrc/dp_clean.hip, no Open3D, no host read-back.
 """
 
 from __future__ import annotations
@@ -358,6 +362,152 @@ def ground_adjust(points: torch.Tensor, grid_size: int = 20, percentile: float =
     check(lib.dp_ground_adjust(pts.data_ptr(), out.data_ptr(), cptr, n, g, float(percentile), stats.data_ptr(),
                                ws.data_ptr(), ws.numel(), stream), "dp_ground_adjust")
     return out, stats
+
+
+# ---- cleaning: stray points, shadow columns (csrc/dp_clean.hip) -----------------------------------
+
+STRAY_STATS = ("finite", "non_finite", "kept", "removed", "error", "reserved0", "reserved1", "reserved2")
+SHADOW_STATS = ("finite", "non_finite", "columns_occupied", "columns_tested", "columns_removed", "points_removed",
+                "cell_size", "error")
+
+
+def _clean_args(points: torch.Tensor, count):
+    if points.device.type != "cuda":
+        raise _lib.DPError("point-cloud cleaning runs on the ROCm device (csrc/dp_clean.hip)")
+    if points.dtype != torch.float64 or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("points must be an (N, 3) float64 tensor")
+    pts = points.contiguous()
+    n = pts.shape[0]
+    if n >= 2 ** 31:
+        raise ValueError("at most 2^31 - 1 points")
+    if count is not None:
+        if not torch.is_tensor(count):
+            count = torch.tensor([int(count)], dtype=torch.int32, device=pts.device)
+        count = count.detach().to(device=pts.device, dtype=torch.int32).reshape(1)
+    lib = _lib.load()
+    ws = torch.empty(int(lib.dp_clean_workspace_size(n)), dtype=torch.uint8, device=pts.device)
+    stream = torch.cuda.current_stream(pts.device).cuda_stream
+    return lib, pts, n, count, (None if count is None else count.data_ptr()), ws, stream
+
+
+def sort_pairs(keys: torch.Tensor, values: torch.Tensor, count=None, bit_lo: int = 0, bit_hi: int = 64
+               ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Stable ascending radix sort of (key, value) pairs by the key bits [bit_lo, bit_hi)
+    (`dp_sort_pairs`), asynchronous.  keys: (n,) int64 / uint64 (sorted as unsigned 64-bit patterns),
+    values: (n,) int32 / uint32.  Returns sorted copies; with `count` (int or device int32) only the
+    first `count` pairs are sorted and the others come back unchanged."""
+    if keys.device.type != "cuda":
+        raise _lib.DPError("sort_pairs runs on the ROCm device (dp_sort_pairs)")
+    if keys.dtype not in (torch.int64, torch.uint64) or values.dtype not in (torch.int32, torch.uint32) \
+            or keys.dim() != 1 or values.shape != keys.shape:
+        raise ValueError("keys must be (n,) int64 / uint64 and values (n,) int32 / uint32")
+    if not 0 <= int(bit_lo) <= int(bit_hi) <= 64:
+        raise ValueError("need 0 <= bit_lo <= bit_hi <= 64")
+    k, v = keys.contiguous().clone(), values.contiguous().clone()
+    n, dev = k.shape[0], k.device
+    if n >= 2 ** 31:
+        raise ValueError("at most 2^31 - 1 pairs")
+    if count is not None:
+        if not torch.is_tensor(count):
+            count = torch.tensor([int(count)], dtype=torch.int32, device=dev)
+        count = count.detach().to(device=dev, dtype=torch.int32).reshape(1)
+    lib = _lib.load()
+    ws = torch.empty(int(lib.dp_clean_workspace_size(n)), dtype=torch.uint8, device=dev)
+    check(lib.dp_sort_pairs(k.data_ptr(), v.data_ptr(), None if count is None else count.data_ptr(), n, int(bit_lo),
+                            int(bit_hi), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream),
+          "dp_sort_pairs")
+    return k, v
+
+
+def stray_mask(points: torch.Tensor, count=None, nb_points: int = 20, radius: float = 0.1
+               ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`dp_clean_stray`: (keep (N,) uint8 -- rows past `count` unwritten --, stats (8,) float64 in
+    `STRAY_STATS` order), both on the device, asynchronous."""
+    if int(nb_points) < 1:
+        raise ValueError(f"nb_points must be >= 1 (got {nb_points})")
+    if not (np.isfinite(radius) and float(radius) > 0):
+        raise ValueError(f"radius must be finite and > 0 (got {radius})")
+    lib, pts, n, count, cptr, ws, stream = _clean_args(points, count)
+    keep = torch.empty(n, dtype=torch.uint8, device=pts.device)
+    stats = torch.empty(8, dtype=torch.float64, device=pts.device)
+    check(lib.dp_clean_stray(pts.data_ptr(), cptr, n, float(radius), int(nb_points), keep.data_ptr(), stats.data_ptr(),
+                             ws.data_ptr(), ws.numel(), stream), "dp_clean_stray")
+    return keep, stats
+
+
+def shadow_mask(points: torch.Tensor, count=None, shadow_height_threshold: float = 0.1, max_shadow_angle: float = 75,
+                min_points_per_column: int = 3) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`dp_clean_shadows`: (keep (N,) uint8, stats (8,) float64 in `SHADOW_STATS` order), on the
+    device, asynchronous."""
+    if int(min_points_per_column) < 1:
+        raise ValueError("min_points_per_column must be >= 1")
+    lib, pts, n, count, cptr, ws, stream = _clean_args(points, count)
+    keep = torch.empty(n, dtype=torch.uint8, device=pts.device)
+    stats = torch.empty(8, dtype=torch.float64, device=pts.device)
+    check(lib.dp_clean_shadows(pts.data_ptr(), cptr, n, float(shadow_height_threshold), float(max_shadow_angle),
+                               int(min_points_per_column), keep.data_ptr(), stats.data_ptr(), ws.data_ptr(),
+                               ws.numel(), stream), "dp_clean_shadows")
+    return keep, stats
+
+
+def compact_points(points: torch.Tensor, colors: Optional[torch.Tensor], keep: torch.Tensor, count=None):
+    """`dp_compact_points`: (points buffer (N, 3), colours buffer or None, device int32 count); the
+    first `count` rows are the kept rows in their original order, the rest is uninitialised."""
+    lib, pts, n, count, cptr, ws, stream = _clean_args(points, count)
+    keep = keep.contiguous()
+    if keep.dtype not in (torch.uint8, torch.bool) or keep.shape != (n,):
+        raise ValueError("keep must be an (N,) uint8 / bool tensor")
+    cols = None
+    if colors is not None:
+        cols = colors.contiguous()
+        if cols.dtype != torch.uint8 or tuple(cols.shape) != (n, 3):
+            raise ValueError("colors must be an (N, 3) uint8 tensor")
+    out = torch.empty_like(pts)
+    cout = None if cols is None else torch.empty_like(cols)
+    n_out = torch.empty(1, dtype=torch.int32, device=pts.device)
+    check(lib.dp_compact_points(pts.data_ptr(), None if cols is None else cols.data_ptr(), keep.data_ptr(), cptr, n,
+                                out.data_ptr(), None if cout is None else cout.data_ptr(), n_out.data_ptr(),
+                                ws.data_ptr(), ws.numel(), stream), "dp_compact_points")
+    return out, cout, n_out
+
+
+def remove_stray_points(points: torch.Tensor, colors: Optional[torch.Tensor] = None, count=None, nb_points: int = 20,
+                        radius: float = 0.1):
+    """The reference's `remove_stray_points` (pointcloud_cleaner.py:142-207) on the device:
+    (points buffer (N, 3), colours buffer or None, device int32 count, stats in `STRAY_STATS` order).
+    Asynchronous, no read-back; the first `count` rows are the result.
+    A point is kept iff at least `nb_points` finite points (itself included) lie at squared distance
+    (dx*dx + dy*dy) + dz*dz < radius*radius -- the strict-`<` restatement of Open3D's radius search
+    (Open3D was not at hand to compare with).  Stated differences: points with a non-finite coordinate
+    are removed; a cloud spanning more than 2^21 - 2 cells of edge `radius` on an axis raises
+    stats["error"] and is returned whole."""
+    keep, stats = stray_mask(points, count, nb_points, radius)
+    out, cols, n_out = compact_points(points, colors, keep, count)
+    return out, cols, n_out, stats
+
+
+def clean_shadows(points: torch.Tensor, colors: Optional[torch.Tensor] = None, count=None,
+                  shadow_height_threshold: float = 0.1, max_shadow_angle: float = 75, min_points_per_column: int = 3):
+    """The reference's `clean_shadows` (pointcloud_cleaner.py:209-309) on the device, same return
+    convention as `remove_stray_points` (stats in `SHADOW_STATS` order; stats[6] is the cell size the
+    device derived from the cloud's density).  Stated differences: a column's points are ordered by
+    y with ties in index order (the reference's argsort is unstable above 16 points); points with a
+    non-finite coordinate are in no column and kept; 2^31 or more columns raise stats["error"] and
+    keep everything."""
+    keep, stats = shadow_mask(points, count, shadow_height_threshold, max_shadow_angle, min_points_per_column)
+    out, cols, n_out = compact_points(points, colors, keep, count)
+    return out, cols, n_out, stats
+
+
+def clean_pointcloud(points: torch.Tensor, colors: Optional[torch.Tensor] = None, count=None, nb_points: int = 20,
+                     radius: float = 0.1, shadow_height_threshold: float = 0.1, max_shadow_angle: float = 75,
+                     min_points_per_column: int = 3):
+    """`remove_stray_points` then `clean_shadows` (the reference pipeline's step 2); the shadow
+    stage's density and cell size come from the cloud after stray removal, as in the reference.
+    Returns (points buffer, colours buffer or None, device int32 count, stray stats, shadow stats)."""
+    p1, c1, n1, st1 = remove_stray_points(points, colors, count, nb_points, radius)
+    p2, c2, n2, st2 = clean_shadows(p1, c1, n1, shadow_height_threshold, max_shadow_angle, min_points_per_column)
+    return p2, c2, n2, st1, st2
 
 
 GROUND_JSON = "ground.json"

@@ -231,14 +231,23 @@ def output_name(image_path: str) -> str:
     return f"{os.path.splitext(os.path.basename(image_path))[0]}_depth.png"
 
 
-def plan_frames(image_paths, output_dir: str, world: int, rank: int, resume: bool) -> List[int]:
+def cloud_name(image_path: str, cleaned: bool = False) -> str:
+    """`{base}_points.ply`, or `{base}_clean.ply` (the reference cleaner's file name) with --clean_pointcloud."""
+    return f"{os.path.splitext(os.path.basename(image_path))[0]}_{'clean' if cleaned else 'points'}.ply"
+
+
+def plan_frames(image_paths, output_dir: str, world: int, rank: int, resume: bool, cleaned: bool = False
+                ) -> List[int]:
     """Indices of the frames this rank processes: the frames still to do (all of them, or with
     `resume` those whose output file is missing -- decided by rank 0 alone and broadcast before
-    any rank writes, so every rank shards the same list), dealt round-robin over the ranks."""
+    any rank writes, so every rank shards the same list), dealt round-robin over the ranks.
+    `cleaned` (--clean_pointcloud): a frame also counts as missing without its `{base}_clean.ply`."""
     todo = list(range(len(image_paths)))
     if resume:
         if rank == 0:
-            todo = [k for k in todo if not os.path.exists(os.path.join(output_dir, output_name(image_paths[k])))]
+            done = lambda k: os.path.exists(os.path.join(output_dir, output_name(image_paths[k]))) and (   # noqa: E731
+                not cleaned or os.path.exists(os.path.join(output_dir, cloud_name(image_paths[k], True))))
+            todo = [k for k in todo if not done(k)]
         if world > 1:
             box = [todo]
             dist.broadcast_object_list(box, src=0)
@@ -249,7 +258,8 @@ def plan_frames(image_paths, output_dir: str, world: int, rank: int, resume: boo
 def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_factor=1.0, half_precision=False,
                               colored=True, cmap="turbo", decode_workers=4, encode_workers=None, pointcloud=False,
                               resume=False, model=None, normalize_ground=False, ground_params_dir=None, grid_size=20,
-                              ground_percentile=5, rotation_offset=None):
+                              ground_percentile=5, rotation_offset=None, clean_pointcloud=False, stray_radius=0.1,
+                              stray_neighbors=20):
     """Directory loop (reference :153-206), pipelined decode -> GPU -> encode, frame-sharded across ranks.
 
     Every rank writes its own frames' files; each frame has exactly one owner.  resume=True skips
@@ -265,10 +275,19 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
     broadcasts it) and saved there; it is then reused for every frame, so a fixed camera does not get
     a jittering floor.  rotation_offset ([rx, ry, rz] degrees, `PC.apply_rotation_to_plane`) is
     applied to the plane in use, not to the saved file, so a re-run does not rotate twice.
+    clean_pointcloud=True (implies normalize_ground) then cleans the levelled cloud on the GPU as the
+    reference pipeline's next step does (`PC.clean_pointcloud`: remove_stray_points with stray_neighbors /
+    stray_radius, then clean_shadows) and writes `{base}_clean.ply` in place of `{base}_points.ply`;
+    resume=True then also looks for that file.
     `model`: an already-built (model, transform) pair (tests); default: `_model`.
     Returns the number of frames this rank wrote.
     """
     ground = None
+    clean = None
+    if clean_pointcloud:
+        check_stray(stray_radius, stray_neighbors)
+        normalize_ground = True
+        clean = {"radius": float(stray_radius), "nb": int(stray_neighbors)}
     if normalize_ground:
         check_grid_size(grid_size)
         pointcloud = True
@@ -282,7 +301,7 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
     world, rank = _dist()
     if ground is not None:
         ground["world"], ground["rank"] = world, rank
-    mine = plan_frames(image_paths, output_dir, world, rank, resume)
+    mine = plan_frames(image_paths, output_dir, world, rank, resume, cleaned=clean is not None)
     print(f"[rank {rank}/{world}] Found {len(image_paths)} images, processing {len(mine)}")
     if model is None:
         model = _model(_device(), half_precision)
@@ -339,20 +358,20 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                     host = _image_async(depth, colored, cmap)
                     gpu_img = True
                     if pointcloud:
-                        pc = _points(depth, pred["focallength_px"], image, ground, image_paths[k])
+                        pc = _points(depth, pred["focallength_px"], image, ground, image_paths[k], clean)
                     ev = torch.cuda.Event()
                     ev.record()
                 else:
                     host, ev = depth, None
 
-                def _finish(host=host, ev=ev, path=output_path, pc=pc, base=base_name, status=status,
-                            gpu_img=gpu_img):
+                def _finish(host=host, ev=ev, path=output_path, pc=pc, status=status, gpu_img=gpu_img,
+                            cloud=os.path.join(output_dir, cloud_name(image_paths[k], clean is not None))):
                     if ev is not None:
                         ev.synchronize()
                     if status is not None:
                         status.check()          # raises: this frame is dropped, nothing written
                     if pc is not None:
-                        PC.write_ply_records(os.path.join(output_dir, f"{base}_points.ply"), _points_host(pc))
+                        PC.write_ply_records(cloud, _points_host(pc))
                     if gpu_img:
                         _write_png(path, _host_image(host))
                         return path
@@ -379,6 +398,13 @@ MAX_GRID_SIZE = PC.MAX_GRID
 def check_grid_size(grid_size) -> None:
     if not 1 <= int(grid_size) <= MAX_GRID_SIZE:
         raise ValueError(f"--grid_size must be in [1, {MAX_GRID_SIZE}] (got {grid_size})")
+
+
+def check_stray(radius, neighbors) -> None:
+    if not (np.isfinite(float(radius)) and float(radius) > 0):
+        raise ValueError(f"--stray_radius must be finite and > 0 (got {radius})")
+    if int(neighbors) < 1:
+        raise ValueError(f"--stray_neighbors must be >= 1 (got {neighbors})")
 
 
 def _ground_plane(ground: dict, xyz, count, image_path):
@@ -416,7 +442,7 @@ def _ground_plane(ground: dict, xyz, count, image_path):
     return model
 
 
-def _points(depth: torch.Tensor, f_px, image, ground=None, image_path=None):
+def _points(depth: torch.Tensor, f_px, image, ground=None, image_path=None, clean=None):
     """Queue the frame's point cloud on the GPU (depth_to_3d, img_to_normalized_pointcloud.py:819-856),
     interleaved into PLY vertex records there, and their copy into a pinned host buffer, on the
     current stream, without a host synchronisation: the full-size record buffer + the point count
@@ -433,6 +459,10 @@ def _points(depth: torch.Tensor, f_px, image, ground=None, image_path=None):
             raise RuntimeError("no ground plane (rank 0 could neither load nor fit one)")
         xyz, _ = PC.normalize_to_ground(xyz, plane, count)
         xyz, _ = PC.ground_adjust(xyz, ground["grid"], ground["pct"], count)
+        if clean is not None:
+            # cleaned cloud (--clean_pointcloud): stray points, then shadow columns; the count stays on the device
+            xyz, cols, count = PC.clean_pointcloud(xyz, cols, count, nb_points=clean["nb"], radius=clean["radius"])[:3]
+            count = count.reshape(())
     out = []
     for t in (PC.ply_records_async(xyz, cols), count):
         hbuf = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
@@ -470,8 +500,16 @@ def main():
                         help=f"Grid cells per axis for the ground adjustment (1..{MAX_GRID_SIZE}, default 20)")
     parser.add_argument("--ground_percentile", type=int, default=5,
                         help="Percentile of the lowest points per cell for the ground adjustment (default 5)")
+    parser.add_argument("--clean_pointcloud", action="store_true",
+                        help="Clean the levelled cloud (implies --normalize_ground): remove stray points, then shadow "
+                             "columns; writes {frame}_clean.ply in place of {frame}_points.ply")
+    parser.add_argument("--stray_radius", type=float, default=0.1,
+                        help="Neighbourhood radius of the stray-point removal in metres (default 0.1)")
+    parser.add_argument("--stray_neighbors", type=int, default=20,
+                        help="Neighbours (the point itself included) a point needs within the radius (default 20)")
     parser.add_argument("--resume", action="store_true",
-                        help="Skip frames whose {frame}_depth.png already exists in --output_dir")
+                        help="Skip frames whose {frame}_depth.png (with --clean_pointcloud: and {frame}_clean.ply) "
+                             "already exists in --output_dir")
     parser.add_argument("--colormap", type=str, default="turbo",
                         choices=["turbo", "viridis", "plasma", "inferno", "magma", "cividis", "jet"],
                         help="Colormap for depth visualization")
@@ -480,13 +518,19 @@ def main():
         parser.error(f"--grid_size must be in [1, {MAX_GRID_SIZE}] (got {args.grid_size})")
     if not 0 <= args.ground_percentile <= 100:
         parser.error("--ground_percentile must be in [0, 100]")
+    try:
+        check_stray(args.stray_radius, args.stray_neighbors)
+    except ValueError as e:
+        parser.error(str(e))
     batch_generate_depth_maps(input_dir=args.input_dir, output_dir=args.output_dir, pattern=args.pattern,
                               downscale_factor=args.downscale_factor, half_precision=args.half_precision,
                               colored=not args.raw, cmap=args.colormap, pointcloud=args.pointcloud,
                               resume=args.resume, normalize_ground=args.normalize_ground,
                               ground_params_dir=args.ground_params_dir, grid_size=args.grid_size,
                               ground_percentile=args.ground_percentile,
-                              rotation_offset=[args.rot_x, args.rot_y, args.rot_z])
+                              rotation_offset=[args.rot_x, args.rot_y, args.rot_z],
+                              clean_pointcloud=args.clean_pointcloud, stray_radius=args.stray_radius,
+                              stray_neighbors=args.stray_neighbors)
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()

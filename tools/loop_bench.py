@@ -38,6 +38,8 @@ def main():
     ap.add_argument("--pointcloud", action="store_true")
     ap.add_argument("--normalize-ground", action="store_true",
                     help="level the point clouds (--normalize_ground of the loop; implies --pointcloud)")
+    ap.add_argument("--clean-pointcloud", action="store_true",
+                    help="clean the levelled clouds (--clean_pointcloud of the loop; implies --normalize-ground)")
     ap.add_argument("--raw", action="store_true")
     ap.add_argument("--workers", type=int, default=None,
                     help="decode and encode threads each (default: the loop's own defaults)")
@@ -124,11 +126,15 @@ def main():
     m, transform = model
     torch.cuda.synchronize()
     t_setup = time.time() - t
+    if args.clean_pointcloud:
+        args.normalize_ground = True
     if args.normalize_ground:
         args.pointcloud = True
     kw = dict(colored=not args.raw, pointcloud=args.pointcloud, model=model)
     if args.normalize_ground:
         kw["normalize_ground"] = True
+    if args.clean_pointcloud:
+        kw["clean_pointcloud"] = True
     if args.workers:
         kw.update(decode_workers=args.workers, encode_workers=args.workers)
     import inspect
@@ -214,6 +220,7 @@ def main():
     out = {
         "what": "generate_depth_maps.batch_generate_depth_maps end to end, 1 GPU",
         "frames": args.frames, "size": [W, H], "pointcloud": args.pointcloud, "normalize_ground": args.normalize_ground,
+        "clean_pointcloud": args.clean_pointcloud,
         "raw": args.raw,
         "ply_records": "host (numpy)" if args.ply_host else "GPU",
         "png_writer": "bytes copies" if args.png_copy else "zero-copy parts",

@@ -41,7 +41,7 @@ enum { DP_A_DENSE = 0, DP_A_CONV = 1 };
 enum { DP_STORE_ROWS = 0, DP_STORE_DECONV2X2 = 1, DP_STORE_HEAD_PS = 2 };
 
 /* ABI version of this header; the Python loader refuses a mismatching .so. */
-#define DP_ABI_VERSION 16
+#define DP_ABI_VERSION 17
 int dp_abi_version(void);
 
 /*
@@ -661,6 +661,99 @@ int dp_clean_shadows(const double* points, const int32_t* n_dev, int32_t n_max, 
 int dp_compact_points(const double* points, const uint8_t* colors, const uint8_t* keep, const int32_t* n_dev,
                       int32_t n_max, double* points_out, uint8_t* colors_out, int32_t* n_out_dev, void* workspace,
                       int64_t workspace_bytes, dp_stream_t stream);
+
+/*
+ * ---- Clustered point clouds (ABI 17, csrc/dp_cluster.hip) -----------------------------------------
+ * The per-point part of the reference pipeline's last step, the floor plan: fit_shapes_to_clusters
+ * (simple_pointcloud_viewer.py:332-412) runs DBSCAN(eps=0.2, min_samples=5) on the (-x, z)
+ * coordinates of the points with y >= height_threshold and fits a shape to each cluster.  Here: the
+ * DBSCAN labels, exactly as sklearn computes them, and a table + cluster-ordered index for a host
+ * shape fit (the fits themselves are not built).  The ground and clean sections' conventions hold:
+ * fp64 points [n_max][3], n_dev a device int32 (NULL: n_max; clamped to [0, n_max]), n_max = 0 and
+ * *n_dev = 0 valid, everything on the caller's stream with no synchronisation and no host read-back,
+ * each fp64 product and sum rounded on its own (no FMA), argument errors returned as DP_ERR_* before
+ * any launch.
+ *   workspace  >= dp_cluster_workspace_size(n_max) bytes of device memory, 8-byte aligned, owned by
+ *              the call until the stream has passed it.  About 100 bytes per point (the sort's
+ *              workspace included).
+ *
+ * Specification.  Participants are the live rows that are finite, have y >= height_threshold (test
+ * skipped for a NaN threshold) and are in the sample (below).  Clustering is over (x, z); negating
+ * x, as the reference does, changes no distance and is not done.
+ *   1. Participants i and j are neighbours iff dx*dx + dz*dz <= eps*eps: inclusive, i == j included,
+ *      every product and sum rounded on its own in fp64 (what sklearn's kd-tree evaluates).
+ *   2. A participant is a core point iff it has at least min_samples neighbours.
+ *   3. Two core points are in one cluster iff a chain of core points, each a neighbour of the next,
+ *      joins them.  Clusters are numbered 0, 1, ... in increasing order of their smallest core row.
+ *   4. A non-core participant with a core neighbour gets the smallest cluster number among its core
+ *      neighbours (sklearn expands clusters in that order, so the first to reach it is the smallest);
+ *      without one it is noise: label -1.
+ *   5. Live rows that do not take part get label -2.
+ * Sampling: max_points = 0 clusters every eligible row (finite, high enough); max_points = m > 0 with
+ * e > m eligible rows (e counted on the device) takes an even stride: the k-th eligible row, in row
+ * order from k = 0, takes part iff k == 0 or floor(k m / e) != floor((k - 1) m / e) in 64-bit
+ * integers -- exactly m rows.  e <= m takes them all.  Stated difference: the reference draws an
+ * unseeded np.random.choice(100000); this is deterministic.
+ *
+ * Method.  Cells of edge eps / sqrt(2) * (1 - 2^-20) over (x, z), 21 bits per axis packed with z
+ * lowest, dp_sort_pairs on (cell, row), coordinates gathered into sorted order.  Any two points of
+ * one cell are neighbours in the rounded arithmetic (argument in the source), so a cell with
+ * >= min_samples participants makes them all core and one set without a distance test.  A point's
+ * neighbours lie in the 5 x 5 block of cells around its own; a block row is one key range found by
+ * binary search.  (All 25 cells: with the shrunk edge two points across a corner of the block can
+ * be nearer than eps, so the corners are walked too.)  Core flags count neighbours with an early
+ * exit at min_samples.  Clusters: lock-free union-find over core points in row-index space, the
+ * larger root hooked under the smaller by a CAS on the root's own word, then compressed, so every
+ * root is its cluster's smallest core row; numbering = exclusive scan of the root flags in row
+ * order.  Border points take the minimum over their core neighbours, one hit per dense cell.
+ * Bounds this implementation keeps:
+ *   - no kernel spins on another workgroup's progress; union-find retries on its own CAS only;
+ *   - no thread loops to n_max: per-thread loops run over the contents of at most 25 cells (plus
+ *     binary searches);
+ *   - k coincident points cost O(k log n), not k^2 distance tests (the dense-cell rule);
+ *   - an axis that would need more than 2^21 - 3 cells ((max - min) / edge over the participants)
+ *     raises the device-side error flag: every participant is labelled -1 and *n_clusters_dev = 0.
+ *     Nothing is labelled from a wrong neighbourhood.
+ */
+int64_t dp_cluster_workspace_size(int64_t n_max);
+
+/*
+ * dp_cluster_dbscan:
+ *   labels_out      int32 [n_max], written for live rows only: cluster number, -1 noise, -2 not a
+ *                   participant
+ *   n_clusters_dev  device int32: the number of clusters
+ *   stats_out       fp64 [8]: finite points, non-finite points, participants, core points, border
+ *                   points, noise points, clusters, error flag
+ * eps not finite or <= 0, min_samples < 1, max_points < 0 (or n_max < 0): DP_ERR_SHAPE.
+ * The call leaves the clusters' smallest core rows in the head of its workspace, for
+ * dp_cluster_table.
+ */
+int dp_cluster_dbscan(const double* points, const int32_t* n_dev, int32_t n_max, double eps, int32_t min_samples,
+                      double height_threshold, int32_t max_points, int32_t* labels_out, int32_t* n_clusters_dev,
+                      double* stats_out, void* workspace, int64_t workspace_bytes, dp_stream_t stream);
+
+/*
+ * dp_cluster_table: per-cluster rows and the cluster-ordered index, K = min(*n_clusters_dev,
+ * max_clusters) clusters.
+ *   table_out    fp64 [max_clusters][12], rows c < K written: count, smallest core row, x min, x max,
+ *                z min, z max, y min, y max, sum x, sum y, sum z, 0.  Count and bounds are exact;
+ *                a sum is accumulated in an unspecified order (wave-level sums, then fp64 atomics),
+ *                so within (count - 1) * 2^-53 * sum |v| of the exact one.
+ *   order_out    uint32 [n_max]: the rows with label >= 0, grouped by cluster and in row order inside
+ *                a cluster (dp_sort_pairs on (label, row)); entries past their number are not written.
+ *   offsets_out  int32 [max_clusters + 1], entries c <= K written: cluster c's members are
+ *                order_out[offsets_out[c] : offsets_out[c + 1]] -- the reference's
+ *                points_2d[labels == c] without a pass per cluster.
+ * The smallest core row cannot be read off the labels (a border point may have a smaller row), so it
+ * is taken from the workspace: pass the workspace of the dp_cluster_dbscan call that produced
+ * `labels` (same n_max, not used by anything else in between) and column 1 is that cluster's
+ * smallest core row; in any other workspace -- zero-filled at least in its first 256 bytes --
+ * column 1 is -1.  Everything else depends on points and labels alone.  max_clusters < 0 (or
+ * n_max < 0): DP_ERR_SHAPE.
+ */
+int dp_cluster_table(const double* points, const int32_t* labels, const int32_t* n_dev, int32_t n_max,
+                     const int32_t* n_clusters_dev, int32_t max_clusters, double* table_out, uint32_t* order_out,
+                     int32_t* offsets_out, void* workspace, int64_t workspace_bytes, dp_stream_t stream);
 
 #ifdef __cplusplus
 }

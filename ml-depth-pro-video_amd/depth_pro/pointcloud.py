@@ -16,6 +16,10 @@ Not built: `optimize_ground_plane` (scipy) and the 50 000-point random pre-sampl
 Cleaning (the reference pipeline's next step, `pointcloud_cleaner.py:142-309`): `remove_stray_points`,
 `clean_shadows` and `clean_pointcloud` (one after the other), on the stable device radix sort
 `sort_pairs` and an order-preserving compaction -- csrc/dp_clean.hip, no Open3D, no host read-back.
+
+Clustering (the per-point part of the floor-plan step, `simple_pointcloud_viewer.py:332-412`):
+`dbscan_labels` (sklearn's DBSCAN labels over (x, z), exactly), `cluster_table`, `cluster_pointcloud`
+and the host-side `cluster_summary` -- csrc/dp_cluster.hip, no sklearn, no host read-back.
 """
 
 from __future__ import annotations
@@ -508,6 +512,123 @@ def clean_pointcloud(points: torch.Tensor, colors: Optional[torch.Tensor] = None
     p1, c1, n1, st1 = remove_stray_points(points, colors, count, nb_points, radius)
     p2, c2, n2, st2 = clean_shadows(p1, c1, n1, shadow_height_threshold, max_shadow_angle, min_points_per_column)
     return p2, c2, n2, st1, st2
+
+
+# ---- clustering: exact DBSCAN labels over (x, z), cluster table (csrc/dp_cluster.hip) --------------
+
+CLUSTER_STATS = ("finite", "non_finite", "participants", "core", "border", "noise", "clusters", "error")
+CLUSTER_COLUMNS = ("count", "min_core_row", "x_min", "x_max", "z_min", "z_max", "y_min", "y_max", "sum_x", "sum_y",
+                   "sum_z", "reserved")
+
+
+def _cluster_args(points: torch.Tensor, count):
+    if points.device.type != "cuda":
+        raise _lib.DPError("point-cloud clustering runs on the ROCm device (csrc/dp_cluster.hip)")
+    if points.dtype != torch.float64 or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("points must be an (N, 3) float64 tensor")
+    pts = points.contiguous()
+    n = pts.shape[0]
+    if n >= 2 ** 31:
+        raise ValueError("at most 2^31 - 1 points")
+    if count is not None:
+        if not torch.is_tensor(count):
+            count = torch.tensor([int(count)], dtype=torch.int32, device=pts.device)
+        count = count.detach().to(device=pts.device, dtype=torch.int32).reshape(1)
+    stream = torch.cuda.current_stream(pts.device).cuda_stream
+    return _lib.load(), pts, n, count, (None if count is None else count.data_ptr()), stream
+
+
+def _check_cluster(eps, min_samples, max_points) -> None:
+    if not (np.isfinite(float(eps)) and float(eps) > 0):
+        raise ValueError(f"eps must be finite and > 0 (got {eps})")
+    if int(min_samples) < 1:
+        raise ValueError(f"min_samples must be >= 1 (got {min_samples})")
+    if int(max_points) < 0:
+        raise ValueError(f"max_points must be >= 0 (got {max_points})")
+
+
+def dbscan_labels(points: torch.Tensor, count=None, eps: float = 0.2, min_samples: int = 5,
+                  height_threshold: Optional[float] = None, max_points: int = 0
+                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """`dp_cluster_dbscan`: the labels sklearn's `DBSCAN(eps, min_samples).fit(points[:, [0, 2]])` gives
+    the participants -- the finite rows with y >= `height_threshold` (None / NaN: every height), thinned
+    to an even stride of `max_points` rows when there are more (0: all) -- as (labels (N,) int32:
+    cluster number, -1 noise, -2 not a participant; rows past `count` unwritten --, device int32 cluster
+    count, stats (8,) float64 in `CLUSTER_STATS` order).  On the device, asynchronous, no read-back.
+    The returned labels keep the call's workspace alive (it holds the clusters' smallest core rows,
+    which `cluster_table` reports)."""
+    _check_cluster(eps, min_samples, max_points)
+    lib, pts, n, count, cptr, stream = _cluster_args(points, count)
+    thr = float("nan") if height_threshold is None else float(height_threshold)
+    ws = torch.empty(int(lib.dp_cluster_workspace_size(n)), dtype=torch.uint8, device=pts.device)
+    labels = torch.empty(n, dtype=torch.int32, device=pts.device)
+    ncl = torch.empty((), dtype=torch.int32, device=pts.device)
+    stats = torch.empty(8, dtype=torch.float64, device=pts.device)
+    check(lib.dp_cluster_dbscan(pts.data_ptr(), cptr, n, float(eps), int(min_samples), thr, int(max_points),
+                                labels.data_ptr(), ncl.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(), stream),
+          "dp_cluster_dbscan")
+    labels._dp_cluster_ws = ws
+    return labels, ncl, stats
+
+
+def cluster_table(points: torch.Tensor, labels: torch.Tensor, n_clusters: torch.Tensor, count=None,
+                  max_clusters: int = 4096) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """`dp_cluster_table`: (table (max_clusters, 12) float64 in `CLUSTER_COLUMNS` order, order (N,)
+    int32, offsets (max_clusters + 1,) int32), on the device, asynchronous.  With K = min(n_clusters,
+    max_clusters), rows c < K of the table and entries c <= K of the offsets are written; cluster c's
+    rows are `order[offsets[c]:offsets[c + 1]]`, ascending.  `min_core_row` is known for labels that
+    come straight from `dbscan_labels` (for any other labels tensor it is -1)."""
+    if int(max_clusters) < 0:
+        raise ValueError(f"max_clusters must be >= 0 (got {max_clusters})")
+    lib, pts, n, count, cptr, stream = _cluster_args(points, count)
+    if labels.device != pts.device or not torch.is_tensor(n_clusters) or n_clusters.device != pts.device:
+        raise _lib.DPError("labels and n_clusters must be on the points' device")
+    if labels.dtype != torch.int32 or tuple(labels.shape) != (n,) or not labels.is_contiguous():
+        raise ValueError("labels must be a contiguous (N,) int32 tensor")
+    if n_clusters.dtype != torch.int32 or n_clusters.numel() != 1:
+        raise ValueError("n_clusters must be a device int32 scalar")
+    need = int(lib.dp_cluster_workspace_size(n))
+    ws = getattr(labels, "_dp_cluster_ws", None)
+    if ws is None or ws.numel() < need or ws.device != pts.device:
+        ws = torch.zeros(need, dtype=torch.uint8, device=pts.device)
+    mc = int(max_clusters)
+    table = torch.zeros(mc, 12, dtype=torch.float64, device=pts.device)
+    order = torch.empty(n, dtype=torch.int32, device=pts.device)
+    offsets = torch.zeros(mc + 1, dtype=torch.int32, device=pts.device)
+    check(lib.dp_cluster_table(pts.data_ptr(), labels.data_ptr(), cptr, n, n_clusters.data_ptr(), mc,
+                               table.data_ptr(), order.data_ptr(), offsets.data_ptr(), ws.data_ptr(), ws.numel(),
+                               stream), "dp_cluster_table")
+    return table, order, offsets
+
+
+def cluster_pointcloud(points: torch.Tensor, count=None, eps: float = 0.2, min_samples: int = 5,
+                       height_threshold: Optional[float] = 1.3, max_points: int = 100000, max_clusters: int = 4096):
+    """`dbscan_labels` then `cluster_table`, with the reference's `fit_shapes_to_clusters` defaults
+    (eps 0.2, min_samples 5, y >= 1.3, at most 100 000 points).  Returns (labels, n_clusters, stats,
+    table, order, offsets), all on the device, nothing synchronised."""
+    labels, ncl, stats = dbscan_labels(points, count, eps, min_samples, height_threshold, max_points)
+    table, order, offsets = cluster_table(points, labels, ncl, count, max_clusters)
+    return labels, ncl, stats, table, order, offsets
+
+
+def cluster_summary(table_host, stats_host, params: Optional[dict] = None) -> dict:
+    """The `{base}_clusters.json` content from arrays already on the host: `table_host` (K, 12) rows of
+    `cluster_table` (K clusters), `stats_host` (8,) in `CLUSTER_STATS` order.  Host only."""
+    t = np.asarray(table_host, dtype=np.float64).reshape(-1, 12)
+    st = np.asarray(stats_host, dtype=np.float64).reshape(8)
+    clusters = []
+    for c, r in enumerate(t):
+        cnt = int(r[0])
+        clusters.append({
+            "id": c, "count": cnt, "min_core_row": int(r[1]),
+            "bbox": {"x": [float(r[2]), float(r[3])], "z": [float(r[4]), float(r[5])], "y": [float(r[6]), float(r[7])]},
+            "centroid": [float(r[8] / cnt), float(r[9] / cnt), float(r[10] / cnt)] if cnt else None,
+        })
+    out = {"parameters": dict(params or {})}
+    out.update({k: int(v) for k, v in zip(CLUSTER_STATS, st)})
+    out["clusters_listed"] = len(clusters)
+    out["cluster_table"] = clusters
+    return out
 
 
 GROUND_JSON = "ground.json"

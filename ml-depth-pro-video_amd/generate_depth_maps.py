@@ -236,17 +236,28 @@ def cloud_name(image_path: str, cleaned: bool = False) -> str:
     return f"{os.path.splitext(os.path.basename(image_path))[0]}_{'clean' if cleaned else 'points'}.ply"
 
 
-def plan_frames(image_paths, output_dir: str, world: int, rank: int, resume: bool, cleaned: bool = False
-                ) -> List[int]:
+def clusters_name(image_path: str) -> str:
+    """`{base}_clusters.json` (--cluster_pointcloud); the labels go to `{base}_labels.npy` beside it."""
+    return f"{os.path.splitext(os.path.basename(image_path))[0]}_clusters.json"
+
+
+def labels_name(image_path: str) -> str:
+    return f"{os.path.splitext(os.path.basename(image_path))[0]}_labels.npy"
+
+
+def plan_frames(image_paths, output_dir: str, world: int, rank: int, resume: bool, cleaned: bool = False,
+                clustered: bool = False) -> List[int]:
     """Indices of the frames this rank processes: the frames still to do (all of them, or with
     `resume` those whose output file is missing -- decided by rank 0 alone and broadcast before
     any rank writes, so every rank shards the same list), dealt round-robin over the ranks.
-    `cleaned` (--clean_pointcloud): a frame also counts as missing without its `{base}_clean.ply`."""
+    `cleaned` (--clean_pointcloud): a frame also counts as missing without its `{base}_clean.ply`;
+    `clustered` (--cluster_pointcloud): and without its `{base}_clusters.json`."""
     todo = list(range(len(image_paths)))
     if resume:
         if rank == 0:
             done = lambda k: os.path.exists(os.path.join(output_dir, output_name(image_paths[k]))) and (   # noqa: E731
-                not cleaned or os.path.exists(os.path.join(output_dir, cloud_name(image_paths[k], True))))
+                not cleaned or os.path.exists(os.path.join(output_dir, cloud_name(image_paths[k], True)))) and (
+                not clustered or os.path.exists(os.path.join(output_dir, clusters_name(image_paths[k]))))
             todo = [k for k in todo if not done(k)]
         if world > 1:
             box = [todo]
@@ -259,7 +270,8 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                               colored=True, cmap="turbo", decode_workers=4, encode_workers=None, pointcloud=False,
                               resume=False, model=None, normalize_ground=False, ground_params_dir=None, grid_size=20,
                               ground_percentile=5, rotation_offset=None, clean_pointcloud=False, stray_radius=0.1,
-                              stray_neighbors=20):
+                              stray_neighbors=20, cluster_pointcloud=False, cluster_eps=0.2, cluster_min_samples=5,
+                              cluster_height=1.3, cluster_max_points=100000):
     """Directory loop (reference :153-206), pipelined decode -> GPU -> encode, frame-sharded across ranks.
 
     Every rank writes its own frames' files; each frame has exactly one owner.  resume=True skips
@@ -279,11 +291,23 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
     reference pipeline's next step does (`PC.clean_pointcloud`: remove_stray_points with stray_neighbors /
     stray_radius, then clean_shadows) and writes `{base}_clean.ply` in place of `{base}_points.ply`;
     resume=True then also looks for that file.
+    cluster_pointcloud=True (implies clean_pointcloud) clusters the cleaned cloud's top-down projection as
+    the reference's floor-plan step does (`PC.cluster_pointcloud`: DBSCAN with cluster_eps /
+    cluster_min_samples over the points with y >= cluster_height -- NaN: every height --, thinned to
+    cluster_max_points, 0 = all) and writes `{base}_clusters.json` (parameters, counts, per-cluster count,
+    bounding box, centroid, smallest core row) and `{base}_labels.npy` (int32, in the row order of
+    `{base}_clean.ply`) beside the cloud; queued on the frame's stream like every other output.
     `model`: an already-built (model, transform) pair (tests); default: `_model`.
     Returns the number of frames this rank wrote.
     """
     ground = None
     clean = None
+    cluster = None
+    if cluster_pointcloud:
+        check_cluster(cluster_eps, cluster_min_samples, cluster_max_points)
+        clean_pointcloud = True
+        cluster = {"eps": float(cluster_eps), "min_samples": int(cluster_min_samples),
+                   "height_threshold": float(cluster_height), "max_points": int(cluster_max_points)}
     if clean_pointcloud:
         check_stray(stray_radius, stray_neighbors)
         normalize_ground = True
@@ -301,7 +325,8 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
     world, rank = _dist()
     if ground is not None:
         ground["world"], ground["rank"] = world, rank
-    mine = plan_frames(image_paths, output_dir, world, rank, resume, cleaned=clean is not None)
+    mine = plan_frames(image_paths, output_dir, world, rank, resume, cleaned=clean is not None,
+                       clustered=cluster is not None)
     print(f"[rank {rank}/{world}] Found {len(image_paths)} images, processing {len(mine)}")
     if model is None:
         model = _model(_device(), half_precision)
@@ -358,20 +383,24 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                     host = _image_async(depth, colored, cmap)
                     gpu_img = True
                     if pointcloud:
-                        pc = _points(depth, pred["focallength_px"], image, ground, image_paths[k], clean)
+                        pc = _points(depth, pred["focallength_px"], image, ground, image_paths[k], clean, cluster)
                     ev = torch.cuda.Event()
                     ev.record()
                 else:
                     host, ev = depth, None
 
                 def _finish(host=host, ev=ev, path=output_path, pc=pc, status=status, gpu_img=gpu_img,
-                            cloud=os.path.join(output_dir, cloud_name(image_paths[k], clean is not None))):
+                            cloud=os.path.join(output_dir, cloud_name(image_paths[k], clean is not None)),
+                            cjson=os.path.join(output_dir, clusters_name(image_paths[k])),
+                            cnpy=os.path.join(output_dir, labels_name(image_paths[k]))):
                     if ev is not None:
                         ev.synchronize()
                     if status is not None:
                         status.check()          # raises: this frame is dropped, nothing written
                     if pc is not None:
                         PC.write_ply_records(cloud, _points_host(pc))
+                        if cluster is not None:
+                            _write_clusters(pc, cluster, cjson, cnpy)
                     if gpu_img:
                         _write_png(path, _host_image(host))
                         return path
@@ -405,6 +434,18 @@ def check_stray(radius, neighbors) -> None:
         raise ValueError(f"--stray_radius must be finite and > 0 (got {radius})")
     if int(neighbors) < 1:
         raise ValueError(f"--stray_neighbors must be >= 1 (got {neighbors})")
+
+
+def check_cluster(eps, min_samples, max_points) -> None:
+    if not (np.isfinite(float(eps)) and float(eps) > 0):
+        raise ValueError(f"--cluster_eps must be finite and > 0 (got {eps})")
+    if int(min_samples) < 1:
+        raise ValueError(f"--cluster_min_samples must be >= 1 (got {min_samples})")
+    if int(max_points) < 0:
+        raise ValueError(f"--cluster_max_points must be >= 0 (got {max_points})")
+
+
+MAX_CLUSTERS = 4096     # rows of the per-frame cluster table (a frame with more lists the first 4096)
 
 
 def _ground_plane(ground: dict, xyz, count, image_path):
@@ -442,7 +483,7 @@ def _ground_plane(ground: dict, xyz, count, image_path):
     return model
 
 
-def _points(depth: torch.Tensor, f_px, image, ground=None, image_path=None, clean=None):
+def _points(depth: torch.Tensor, f_px, image, ground=None, image_path=None, clean=None, cluster=None):
     """Queue the frame's point cloud on the GPU (depth_to_3d, img_to_normalized_pointcloud.py:819-856),
     interleaved into PLY vertex records there, and their copy into a pinned host buffer, on the
     current stream, without a host synchronisation: the full-size record buffer + the point count
@@ -463,8 +504,13 @@ def _points(depth: torch.Tensor, f_px, image, ground=None, image_path=None, clea
             # cleaned cloud (--clean_pointcloud): stray points, then shadow columns; the count stays on the device
             xyz, cols, count = PC.clean_pointcloud(xyz, cols, count, nb_points=clean["nb"], radius=clean["radius"])[:3]
             count = count.reshape(())
+    extra = ()
+    if cluster is not None:
+        # clusters of the cleaned cloud (--cluster_pointcloud): labels, table and counts, same stream, no sync
+        labels, ncl, stats, table, _, _ = PC.cluster_pointcloud(xyz, count, max_clusters=MAX_CLUSTERS, **cluster)
+        extra = (labels, ncl, stats, table)
     out = []
-    for t in (PC.ply_records_async(xyz, cols), count):
+    for t in (PC.ply_records_async(xyz, cols), count) + extra:
         hbuf = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
         hbuf.copy_(t, non_blocking=True)
         out.append(hbuf)
@@ -473,8 +519,20 @@ def _points(depth: torch.Tensor, f_px, image, ground=None, image_path=None, clea
 
 def _points_host(pc):
     """Writer-thread side (after the frame's event): exactly the valid points' records."""
-    rec, n_host = pc
+    rec, n_host = pc[:2]
     return rec[:int(n_host)].numpy()
+
+
+def _write_clusters(pc, cluster: dict, json_path: str, npy_path: str) -> None:
+    """Writer-thread side: `{base}_labels.npy` (the live rows' labels) and `{base}_clusters.json`."""
+    import json
+
+    n, (labels, ncl, stats, table) = int(pc[1]), pc[2:]
+    np.save(npy_path, labels[:n].numpy())
+    k = min(int(ncl), MAX_CLUSTERS)
+    with open(json_path, "w") as f:
+        params = {key: (None if isinstance(v, float) and v != v else v) for key, v in cluster.items()}   # NaN height
+        json.dump(PC.cluster_summary(table[:k].numpy(), stats.numpy(), params), f, indent=1)
 
 
 def main():
@@ -507,9 +565,19 @@ def main():
                         help="Neighbourhood radius of the stray-point removal in metres (default 0.1)")
     parser.add_argument("--stray_neighbors", type=int, default=20,
                         help="Neighbours (the point itself included) a point needs within the radius (default 20)")
+    parser.add_argument("--cluster_pointcloud", action="store_true",
+                        help="Cluster the cleaned cloud's top-down projection (implies --clean_pointcloud): DBSCAN "
+                             "labels to {frame}_labels.npy, counts and per-cluster boxes to {frame}_clusters.json")
+    parser.add_argument("--cluster_eps", type=float, default=0.2, help="DBSCAN neighbourhood radius in metres (default 0.2)")
+    parser.add_argument("--cluster_min_samples", type=int, default=5,
+                        help="Neighbours (the point itself included) that make a core point (default 5)")
+    parser.add_argument("--cluster_height", type=float, default=1.3,
+                        help="Cluster the points with y >= this height in metres (default 1.3; nan: every height)")
+    parser.add_argument("--cluster_max_points", type=int, default=100000,
+                        help="Cluster at most this many points, an even stride of the rest (default 100000; 0: all)")
     parser.add_argument("--resume", action="store_true",
-                        help="Skip frames whose {frame}_depth.png (with --clean_pointcloud: and {frame}_clean.ply) "
-                             "already exists in --output_dir")
+                        help="Skip frames whose {frame}_depth.png (with --clean_pointcloud: and {frame}_clean.ply; with "
+                             "--cluster_pointcloud: and {frame}_clusters.json) already exists in --output_dir")
     parser.add_argument("--colormap", type=str, default="turbo",
                         choices=["turbo", "viridis", "plasma", "inferno", "magma", "cividis", "jet"],
                         help="Colormap for depth visualization")
@@ -520,6 +588,7 @@ def main():
         parser.error("--ground_percentile must be in [0, 100]")
     try:
         check_stray(args.stray_radius, args.stray_neighbors)
+        check_cluster(args.cluster_eps, args.cluster_min_samples, args.cluster_max_points)
     except ValueError as e:
         parser.error(str(e))
     batch_generate_depth_maps(input_dir=args.input_dir, output_dir=args.output_dir, pattern=args.pattern,
@@ -530,7 +599,9 @@ def main():
                               ground_percentile=args.ground_percentile,
                               rotation_offset=[args.rot_x, args.rot_y, args.rot_z],
                               clean_pointcloud=args.clean_pointcloud, stray_radius=args.stray_radius,
-                              stray_neighbors=args.stray_neighbors)
+                              stray_neighbors=args.stray_neighbors, cluster_pointcloud=args.cluster_pointcloud,
+                              cluster_eps=args.cluster_eps, cluster_min_samples=args.cluster_min_samples,
+                              cluster_height=args.cluster_height, cluster_max_points=args.cluster_max_points)
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()

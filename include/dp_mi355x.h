@@ -287,6 +287,8 @@ int dp_gemm_plan(const dp_gemm_args* args, int32_t* tile, int32_t* grid);
 /*
  * dp_layernorm: y[r] = LN(x[r]) * w + b over `cols`, fp32 in, 16-bit out.
  * Replaces timm Block norm1/norm2 and the final `norm` (eps 1e-6).
+ * cols: 256, 512, 1024 or 2048; ldx % 4 == 0, ldy % 4 == 0 (% 8 above 256 columns).  x, w and b
+ * must be 16-B aligned, y 8-B aligned at 256 columns and 16-B aligned above (DP_ERR_ALIGN).
  */
 int dp_layernorm(const float* x, int64_t ldx, const float* w, const float* b, void* y, int64_t ldy,
                  int32_t rows, int32_t cols, float eps, int32_t dtype, dp_stream_t stream);
@@ -298,7 +300,8 @@ int dp_layernorm(const float* x, int64_t ldx, const float* w, const float* b, vo
  * producer epilogue writes, for the rows no GEMM produced (the patch embed + cls rows that enter
  * ViT block 0).  xl (ABI 12; NULL: none): the int8 low part of the split residual ([rows][ldxb]
  * bytes, the encoding of dp_gemm_args.ln_xl), so that (xb, xl) is the stream a split-residual
- * producer reads.
+ * producer reads.  ldx % 4 == 0, ldxb % 8 == 0; x and xb must be 16-B aligned, xl and part 8-B
+ * aligned (DP_ERR_ALIGN).
  */
 int dp_layernorm_stats(const float* x, int64_t ldx, int32_t rows, int32_t cols, void* xb, int64_t ldxb,
                        void* xl, float* part, int32_t dtype, dp_stream_t stream);
@@ -306,7 +309,8 @@ int dp_layernorm_stats(const float* x, int64_t ldx, int32_t rows, int32_t cols, 
 /*
  * dp_layernorm_grouped: dp_layernorm over groups * rows_per_group rows, rows of group g taking
  * w[g] / b[g] (w, b: HOST arrays of `groups` (1..4) device pointers) -- the image and FOV
- * encoders' norm1 / norm2 / final norm in one launch.
+ * encoders' norm1 / norm2 / final norm in one launch.  Alignment as dp_layernorm, for x, y and
+ * every w[g] / b[g].
  */
 int dp_layernorm_grouped(const float* x, int64_t ldx, const float* const* w, const float* const* b,
                          int32_t groups, void* y, int64_t ldy, int32_t rows_per_group, int32_t cols,
@@ -317,6 +321,9 @@ int dp_layernorm_grouped(const float* x, int64_t ldx, const float* const* w, con
  * qkv: [batch*seq][3*heads*head_dim] (timm's qkv Linear output, (3, heads, hd) column order);
  * out: [batch*seq][heads*head_dim] (timm's transpose(1,2).reshape). head_dim must be 64.
  * Replaces timm Attention's F.scaled_dot_product_attention (scale = head_dim^-0.5).
+ * out = softmax(scale * Q K^T) V per (image, head); scale must be finite and >= 0 (DP_ERR_ARG;
+ * 0 gives the mean of V).  qkv and out must be 16-B aligned (DP_ERR_ALIGN); the launch has
+ * ceil(seq / 128) * heads * batch workgroups, which must stay below 2^31 (DP_ERR_SHAPE).
  */
 int dp_attention(const void* qkv, void* out, int32_t batch, int32_t seq, int32_t heads,
                  int32_t head_dim, float scale, int32_t dtype, dp_stream_t stream);
@@ -325,7 +332,8 @@ int dp_attention(const void* qkv, void* out, int32_t batch, int32_t seq, int32_t
  * dp_attention_log2q: dp_attention for a qkv whose Q columns already hold
  * Q * scale * log2(e) -- folded into the qkv Linear's epilogue as a per-column gamma --
  * so the scores leave the MFMA in log2 units and the softmax needs one exp2 per score.
- * Same result as dp_attention up to where the scale is rounded (before the 16-bit Q).
+ * Same result as dp_attention up to where the scale is rounded (before the 16-bit Q); the same
+ * alignment and size rules.
  */
 int dp_attention_log2q(const void* qkv, void* out, int32_t batch, int32_t seq, int32_t heads,
                        int32_t head_dim, int32_t dtype, dp_stream_t stream);

@@ -259,8 +259,14 @@ attn_kernel(const u16* __restrict__ qkv, u16* __restrict__ out, int seq, int hea
           p0 = __builtin_amdgcn_exp2f(s[8 * st + 2 * jj]);
           p1 = __builtin_amdgcn_exp2f(s[8 * st + 2 * jj + 1]);
         } else {
-          p0 = __builtin_amdgcn_exp2f(fmaf(s[8 * st + 2 * jj], sl2, -m_run));
-          p1 = __builtin_amdgcn_exp2f(fmaf(s[8 * st + 2 * jj + 1], sl2, -m_run));
+          float a0 = fmaf(s[8 * st + 2 * jj], sl2, -m_run);
+          float a1 = fmaf(s[8 * st + 2 * jj + 1], sl2, -m_run);
+          if constexpr (PARTIAL) {   // a masked key stays masked whatever the scale (-inf * 0 is NaN)
+            if (s[8 * st + 2 * jj] == -INFINITY) a0 = -INFINITY;
+            if (s[8 * st + 2 * jj + 1] == -INFINITY) a1 = -INFINITY;
+          }
+          p0 = __builtin_amdgcn_exp2f(a0);
+          p1 = __builtin_amdgcn_exp2f(a1);
         }
         w[jj] = K_::pack2(p0, p1);
         if (!ABL(16)) ls4[0] = (ls4[0] + p0) + p1;
@@ -445,6 +451,11 @@ int attention_launch(const void* qkv, void* out, int32_t batch, int32_t seq, int
                      float scale, bool pre, int32_t dtype, dp_stream_t stream) {
   if (!qkv || !out) return DP_ERR_ARG;
   if (batch <= 0 || seq <= 0 || heads <= 0 || head_dim != HD) return DP_ERR_SHAPE;
+  if (dtype != DP_BF16 && dtype != DP_F16) return DP_ERR_DTYPE;
+  // the running max is max(score) * scale: a negative (or non-finite) scale would turn it into the min
+  if (!pre && !(scale >= 0.f && scale <= 3.0e38f)) return DP_ERR_ARG;
+  // every Q / K / V load, LDS-DMA piece and output store is 16 B wide (rows are 128 B multiples)
+  if ((uintptr_t)qkv % 16 || (uintptr_t)out % 16) return DP_ERR_ALIGN;
   // Measured and rejected (35 x 577): two independent 32-query sub-blocks per wave (K / V
   // fragments shared, 210 VGPRs, 2 workgroups per CU) 98-101 us vs 75-76 us here -- the
   // occupancy (4 workgroups / 16 waves per CU) hides more than the in-wave ILP adds.
@@ -454,7 +465,6 @@ int attention_launch(const void* qkv, void* out, int32_t batch, int32_t seq, int
   // softmax(s * scale) = 2^(s * scale * log2 e) / sum: sl2 is the scale in log2 units
   const float sl2 = pre ? 1.0f : (float)((double)scale * 1.4426950408889634);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype != DP_BF16 && dtype != DP_F16) return DP_ERR_DTYPE;
   if (pre) {
     if (dtype == DP_BF16) hipLaunchKernelGGL((attn_kernel<KBF16, true>), grid, dim3(256), 0, s, (const u16*)qkv, (u16*)out, seq, heads, nq, sl2, g_attn_dbg);
     else hipLaunchKernelGGL((attn_kernel<KF16, true>), grid, dim3(256), 0, s, (const u16*)qkv, (u16*)out, seq, heads, nq, sl2, g_attn_dbg);

@@ -553,6 +553,8 @@ extern "C" int dp_layernorm_stats(const float* x, int64_t ldx, int32_t rows, int
   if (!x || !xb || !part) return DP_ERR_ARG;
   if (rows <= 0) return DP_ERR_SHAPE;
   if (ldx % 4 || ldxb % 8) return DP_ERR_ALIGN;
+  // 16-B loads of x and stores of xb, 8-B stores of xl and of part's (mean, M2) pairs
+  if ((uintptr_t)x % 16 || (uintptr_t)xb % 16 || (uintptr_t)xl % 8 || (uintptr_t)part % 8) return DP_ERR_ALIGN;
   dim3 grid((rows + 3) / 4);
   hipStream_t s = (hipStream_t)stream;
 #define DP_LS(V_) do { \
@@ -575,6 +577,8 @@ extern "C" int dp_layernorm(const float* x, int64_t ldx, const float* w, const f
   if (!x || !w || !b || !y) return DP_ERR_ARG;
   if (rows <= 0 || ldx % 4 || ldy % 4) return DP_ERR_SHAPE;
   if (cols > 256 && (ldy % 8 || (uintptr_t)y % 16)) return DP_ERR_ALIGN;   // 16-B row stores
+  if ((uintptr_t)y % 8) return DP_ERR_ALIGN;                                // 256 columns: 8-B stores
+  if ((uintptr_t)x % 16 || (uintptr_t)w % 16 || (uintptr_t)b % 16) return DP_ERR_ALIGN;   // float4 loads
   hipStream_t s = (hipStream_t)stream;
   LnW lw{};
   lw.w[0] = w;
@@ -591,9 +595,11 @@ extern "C" int dp_layernorm_grouped(const float* x, int64_t ldx, const float* co
   if (!x || !w || !b || !y || groups < 1 || groups > LN_MAX_GROUPS) return DP_ERR_ARG;
   if (rows_per_group <= 0 || ldx % 4 || ldy % 4) return DP_ERR_SHAPE;
   if (cols > 256 && (ldy % 8 || (uintptr_t)y % 16)) return DP_ERR_ALIGN;
+  if ((uintptr_t)y % 8 || (uintptr_t)x % 16) return DP_ERR_ALIGN;
   LnW lw{};
   for (int g = 0; g < groups; ++g) {
     if (!w[g] || !b[g]) return DP_ERR_ARG;
+    if ((uintptr_t)w[g] % 16 || (uintptr_t)b[g] % 16) return DP_ERR_ALIGN;
     lw.w[g] = w[g];
     lw.b[g] = b[g];
   }

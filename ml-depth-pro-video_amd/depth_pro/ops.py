@@ -398,16 +398,20 @@ def layernorm_grouped(x: torch.Tensor, ws, bs, y: torch.Tensor, rows_per_group: 
 
 
 def attention(qkv: torch.Tensor, out: torch.Tensor, batch: int, seq: int, heads: int = 16,
-              head_dim: int = 64, log2q: bool = False) -> None:
+              head_dim: int = 64, log2q: bool = False, scale: Optional[float] = None) -> None:
     """dp_attention; `log2q=True`: dp_attention_log2q, the Q columns of `qkv` already hold
-    Q * head_dim^-0.5 * log2(e) (see `log2q_gamma`)."""
+    Q * head_dim^-0.5 * log2(e) (see `log2q_gamma`).  `scale` (dp_attention only): the softmax
+    scale, head_dim^-0.5 when None."""
+    if log2q and scale is not None:
+        raise _lib.DPError("dp_attention_log2q takes no scale: it is folded into Q")
     with _Timed("attention", 4.0 * batch * heads * seq * seq * head_dim, (batch, seq), out.dtype):
         if log2q:
             check(_lib.load().dp_attention_log2q(qkv.data_ptr(), out.data_ptr(), batch, seq, heads, head_dim,
                                                  dtype_code(out.dtype), _stream(out)), "dp_attention_log2q")
         else:
             check(_lib.load().dp_attention(qkv.data_ptr(), out.data_ptr(), batch, seq, heads, head_dim,
-                                           head_dim ** -0.5, dtype_code(out.dtype), _stream(out)), "dp_attention")
+                                           head_dim ** -0.5 if scale is None else float(scale),
+                                           dtype_code(out.dtype), _stream(out)), "dp_attention")
 
 
 LOG2E = 1.4426950408889634

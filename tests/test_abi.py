@@ -272,3 +272,72 @@ def test_empty_inputs_are_refused_before_launch():
     assert lib.dp_gemm(ctypes.byref(a), None) == 1001
     a.N = 64
     assert lib.dp_gemm_grouped(ctypes.byref(a), 0, None) == 1000
+
+
+def test_attention_and_layernorm_arguments_are_refused_before_launch():
+    """dp_mi355x.h, dp_attention / dp_layernorm*: the pointer alignments every 16-B (8-B) load and
+    store needs, head_dim, the dtype code, null pointers and the 2^31 grid limit come back as
+    DP_ERR_* from the host (no GPU here: a launch would return a HIP error instead)."""
+    lib = _lib.load()
+    ARG, SHAPE, ALIGN, DTYPE = 1000, 1001, 1002, 1003
+    P = 4096                      # dummy, 16-B aligned, never dereferenced on the host
+    f32 = ctypes.c_float
+    sc = f32(0.125)
+
+    def attn(qkv=P, out=P, batch=1, seq=577, heads=16, hd=64, scale=sc, dt=0):
+        return (lib.dp_attention(qkv, out, batch, seq, heads, hd, scale, dt, None),
+                lib.dp_attention_log2q(qkv, out, batch, seq, heads, hd, dt, None))
+
+    for off in (2, 4, 8):
+        assert attn(qkv=P + off) == (ALIGN, ALIGN), off
+        assert attn(out=P + off) == (ALIGN, ALIGN), off
+    for hd in (32, 63, 128):
+        assert attn(hd=hd) == (SHAPE, SHAPE), hd
+    assert attn(dt=_lib.DP_F32) == (DTYPE, DTYPE)
+    assert attn(dt=7) == (DTYPE, DTYPE)
+    assert attn(qkv=None) == (ARG, ARG) and attn(out=None) == (ARG, ARG)
+    # ceil(seq / 128) * heads * batch workgroups: 2^31 is refused (2^31 - 1 would be launched)
+    assert attn(batch=1 << 20, seq=1, heads=1 << 11) == (SHAPE, SHAPE)
+    assert attn(batch=1 << 20, seq=129, heads=1 << 10) == (SHAPE, SHAPE)
+    assert attn(batch=(1 << 31) - 1, seq=128 * 3, heads=1) == (SHAPE, SHAPE)
+    for bad in (-0.125, float("nan"), float("inf")):
+        assert lib.dp_attention(P, P, 1, 577, 16, 64, f32(bad), 0, None) == ARG, bad
+
+    def ln(x=P, w=P, b=P, y=P, cols=1024, ldx=None, ldy=None, dt=0, rows=5):
+        return lib.dp_layernorm(x, cols if ldx is None else ldx, w, b, y, cols if ldy is None else ldy, rows, cols,
+                                f32(1e-6), dt, None)
+
+    def lng(x=P, w=(P, P), b=(P, P), y=P, cols=1024, dt=0, rpg=3):
+        pw, pb = (ctypes.c_void_p * len(w))(*w), (ctypes.c_void_p * len(b))(*b)
+        return lib.dp_layernorm_grouped(x, cols, pw, pb, len(w), y, cols, rpg, cols, f32(1e-6), dt, None)
+
+    for cols in (256, 512, 1024, 2048):
+        for off in (4, 8):
+            assert ln(x=P + off, cols=cols) == ALIGN, (cols, off)
+            assert ln(w=P + off, cols=cols) == ALIGN, (cols, off)
+            assert ln(b=P + off, cols=cols) == ALIGN, (cols, off)
+            assert lng(x=P + off, cols=cols) == ALIGN, (cols, off)
+            assert lng(w=(P, P + off), cols=cols) == ALIGN, (cols, off)
+            assert lng(b=(P + off, P), cols=cols) == ALIGN, (cols, off)
+        for off in (2, 4, 6):
+            assert ln(y=P + off, cols=cols) == ALIGN, (cols, off)
+            assert lng(y=P + off, cols=cols) == ALIGN, (cols, off)
+        if cols > 256:            # (8-B alignment is enough for the 256-column kernel's stores)
+            assert ln(y=P + 8, cols=cols) == ALIGN and lng(y=P + 8, cols=cols) == ALIGN, cols
+    assert ln(dt=_lib.DP_F32) == DTYPE and lng(dt=_lib.DP_F32) == DTYPE
+    for kw in (dict(x=None), dict(w=None), dict(b=None), dict(y=None)):
+        assert ln(**kw) == ARG, kw
+    assert lng(w=(P, None)) == ARG and lng(x=None) == ARG
+    assert ln(cols=768) == SHAPE and ln(ldx=1026) == SHAPE
+
+    def stats(x=P, xb=P, xl=P, part=P, cols=1024, dt=0):
+        return lib.dp_layernorm_stats(x, cols, 5, cols, xb, cols, xl, part, dt, None)
+
+    for off in (4, 8):
+        assert stats(x=P + off) == ALIGN and stats(xb=P + off) == ALIGN, off
+    for off in (1, 2, 4):
+        assert stats(xl=P + off) == ALIGN, off
+    assert stats(xb=P + 2) == ALIGN and stats(part=P + 4) == ALIGN
+    assert stats(dt=_lib.DP_F32) == DTYPE
+    assert stats(x=None) == ARG and stats(xb=None) == ARG and stats(part=None) == ARG
+    assert stats(cols=256) == SHAPE

@@ -41,7 +41,7 @@ enum { DP_A_DENSE = 0, DP_A_CONV = 1 };
 enum { DP_STORE_ROWS = 0, DP_STORE_DECONV2X2 = 1, DP_STORE_HEAD_PS = 2 };
 
 /* ABI version of this header; the Python loader refuses a mismatching .so. */
-#define DP_ABI_VERSION 17
+#define DP_ABI_VERSION 18
 int dp_abi_version(void);
 
 /*
@@ -675,8 +675,8 @@ int dp_compact_points(const double* points, const uint8_t* colors, const uint8_t
  * The per-point part of the reference pipeline's last step, the floor plan: fit_shapes_to_clusters
  * (simple_pointcloud_viewer.py:332-412) runs DBSCAN(eps=0.2, min_samples=5) on the (-x, z)
  * coordinates of the points with y >= height_threshold and fits a shape to each cluster.  Here: the
- * DBSCAN labels, exactly as sklearn computes them, and a table + cluster-ordered index for a host
- * shape fit (the fits themselves are not built).  The ground and clean sections' conventions hold:
+ * DBSCAN labels, exactly as sklearn computes them, and a table + cluster-ordered index for the
+ * shape fit (the fits themselves: "Cluster shapes", ABI 18, below).  The ground and clean sections' conventions hold:
  * fp64 points [n_max][3], n_dev a device int32 (NULL: n_max; clamped to [0, n_max]), n_max = 0 and
  * *n_dev = 0 valid, everything on the caller's stream with no synchronisation and no host read-back,
  * each fp64 product and sum rounded on its own (no FMA), argument errors returned as DP_ERR_* before
@@ -762,6 +762,105 @@ int dp_cluster_dbscan(const double* points, const int32_t* n_dev, int32_t n_max,
 int dp_cluster_table(const double* points, const int32_t* labels, const int32_t* n_dev, int32_t n_max,
                      const int32_t* n_clusters_dev, int32_t max_clusters, double* table_out, uint32_t* order_out,
                      int32_t* offsets_out, void* workspace, int64_t workspace_bytes, dp_stream_t stream);
+
+/*
+ * ---- Cluster shapes (ABI 18, csrc/dp_shapes.hip) ---------------------------------------------------
+ * The rest of the reference's floor-plan step: per cluster the convex hull, the minimum-area
+ * rectangle, the least-squares circle and the circle-or-rectangle decision of fit_shapes_to_clusters
+ * (simple_pointcloud_viewer.py:332-412, fit_circle :12-42, is_better_fit_as_circle :44-77), from the
+ * order / offsets / cluster count of a dp_cluster_table call.  The ground, clean and cluster
+ * sections' conventions hold: fp64 points [n_max][3], n_dev a device int32 (NULL: n_max; clamped to
+ * [0, n_max]), n_max = 0, *n_dev = 0 and zero clusters valid, everything on the caller's stream with
+ * no synchronisation and no host read-back, each fp64 product, sum and difference rounded on its own
+ * (no FMA), argument errors returned as DP_ERR_* before any launch.
+ *   workspace  >= dp_shapes_workspace_size(n_max, max_clusters) bytes of device memory, 8-byte
+ *              aligned, owned by the call until the stream has passed it (content need not be
+ *              initialised).  About 28 bytes per point and 40 per cluster.
+ *
+ * Frame.  Shapes are fitted in the reference's top-down frame u = -x, v = z
+ * (simple_pointcloud_viewer.py / pointcloud_pipeline.py:111-118).  The negation is exact; it makes
+ * centres and angles the reference's numbers (the cluster stage, which only measures distances, did
+ * not need it).
+ *
+ * Specification.  For each cluster c < K = min(*n_clusters_dev, max_clusters), members
+ * order[offsets[c] : offsets[c + 1]] (ascending rows), N of them:
+ *   1. N < 5: skipped, as the reference does (:362).  kind 0, count N, every other column 0.
+ *   2. Convex hull.  o(a, b, c) = (bu - au) * (cv - av) - (bv - av) * (cu - au), every operation
+ *      rounded on its own.  The hull's vertices are the members that are strict corners (o > 0 taken
+ *      counter-clockwise): collinear and duplicate points are not vertices; among coincident members
+ *      the smallest row is the vertex.  They are listed counter-clockwise from the lexicographically
+ *      smallest (u, v): the monotone chain over the members sorted by (u, v, row) with one member per
+ *      distinct (u, v), a point leaving the stack unless o(second from top, top, new) > 0; lower
+ *      hull left to right, then upper hull right to left.  One distinct point gives one vertex, two
+ *      (or any exactly collinear set) two.  hull_area = (sum over i = 1 .. h - 2 of
+ *      o(p_0, p_i, p_i+1)) / 2: the shoelace sum taken from the first vertex, where every term is
+ *      positive (summation order unspecified).
+ *   3. Minimum-area rectangle (rotating calipers), h >= 2.  For every hull edge i, p_i -> p_i+1
+ *      (the last back to p_0), in list order: d = p_i+1 - p_i, len = sqrt(du*du + dv*dv),
+ *      e = (du / len, dv / len), n = (-e_v, e_u); over ALL hull vertices p = u*e_u + v*e_v and
+ *      q = v*e_u - u*e_v; width = max p - min p, height = max q - min q, area = width * height.  The
+ *      smallest area wins, ties go to the smallest i.  With pc = (min p + max p) / 2 and
+ *      qc = (min q + max q) / 2: centre = (e_u*pc - e_v*qc, e_v*pc + e_u*qc),
+ *      angle = atan2(e_v, e_u) * 57.29577951308232 degrees, folded into [0, 90):
+ *      k = floor(angle / 90), angle -= 90 * k, and if that rounds to 90 (a tiny negative angle)
+ *      angle = 0, k += 1; odd k swaps width and height.  h = 1 (N coincident points): a 0 x 0
+ *      rectangle at that point, angle 0, area 0.
+ *      Stated differences from the reference: cv2.minAreaRect works on a float32 copy of the points
+ *      and its angle convention depends on the OpenCV version; this fit is in fp64 on the fp64 points
+ *      and its convention is the one above.
+ *   4. Circle: the reference's fit_circle minimises sum (R_i - mean R)^2 over the centre with
+ *      scipy.optimize.leastsq from the members' mean.  Here the same residuals and start, by a damped
+ *      Gauss-Newton (Levenberg-Marquardt) iteration.  At a centre (x, y): R_i = sqrt((u_i - x)^2 +
+ *      (v_i - y)^2), a_i = (u_i - x) / R_i, b_i = (v_i - y) / R_i (both 0 where R_i = 0); the sums
+ *      SR, Sa, Sb, Saa, Sab, Sbb, SaR, SbR, SRR of R, a, b, a a, a b, b b, a R, b R, R R (summation
+ *      order unspecified); Rm = SR / N, A11 = Saa - Sa*Sa/N, A12 = Sab - Sa*Sb/N,
+ *      A22 = Sbb - Sb*Sb/N, g1 = SaR - Sa*Rm, g2 = SbR - Sb*Rm, cost = SRR - SR*Rm.
+ *      Start: (x, y) = (sum u / N, sum v / N), lambda = 1e-3.  At most 50 times:
+ *        M11 = A11 (1 + lambda), M22 = A22 (1 + lambda), det = M11*M22 - A12*A12; stop unless det > 0;
+ *        dx = (M22*g1 - A12*g2) / det, dy = (M11*g2 - A12*g1) / det; evaluate the sums at
+ *        (x + dx, y + dy);
+ *        if its cost <= cost: move there, lambda /= 10, and stop if sqrt(dx*dx + dy*dy) <= 1e-13 * its Rm;
+ *        else lambda *= 10, and stop if lambda > 1e10.
+ *      xc, yc = the final centre, r = its Rm, fit_error = (sum (R_i - r)^2 / N) / (r*r).
+ *   5. Decision (is_better_fit_as_circle): circle_area = pi * (r*r); h < 3 or hull_area not > 0: a
+ *      rectangle with circ = 0 (where the reference's qhull call raises, and its fallback rule cannot
+ *      say "circle" for a zero rectangle area).  Otherwise circ = hull_area / circle_area,
+ *      circ = min(circ, 1 / circ), and the cluster is a circle iff circ > circularity_threshold and
+ *      fit_error < 0.15 and |circle_area - area| / max(circle_area, area) < 0.3 (area: the
+ *      rectangle's), every comparison false on NaN.
+ *   6. Row c of shapes_out, fp64 [max_clusters][16], rows c < K written: kind (0 skipped, 1 rectangle,
+ *      2 circle), count, rectangle centre u, centre v, width, height, angle, area, circle xc, yc, r,
+ *      fit_error, hull_area, hull vertex count, circ, error flag.
+ *   hull_rows_out     int32 [n_max]: the hulls' vertices as row numbers, cluster after cluster
+ *   hull_offsets_out  int32 [max_clusters + 1], entries c <= K written: cluster c's vertices are
+ *                     hull_rows_out[hull_offsets_out[c] : hull_offsets_out[c + 1]]
+ *
+ * Method.  (u, v) is gathered once into cluster order.  Hulls by exact reduction (the hull of a union
+ * is the hull of the hulls): a cluster's members are cut into chunks of DP_SHAPES_H_MAX; a workgroup
+ * sorts its chunk in LDS by (u, v, row rank) (bitonic), runs the chain (lower and upper hull on two
+ * waves) and writes the survivors back; rounds repeat until the cluster is one chunk, whose hull is
+ * the cluster's; that workgroup then takes the area and the calipers (one lane per edge over the
+ * vertices in LDS, min-reduction with the index tie-break).  Chunk lists are built on the device by
+ * one-workgroup scans.  Circle: one workgroup per cluster streams the gathered members once per
+ * evaluation (wave reductions of the nine sums).
+ * Bounds this implementation keeps:
+ *   - no kernel waits on another workgroup;
+ *   - no thread loops over a whole cluster: the chain's two serial loops run over one chunk
+ *     (<= DP_SHAPES_H_MAX members), the circle's loops over 1/256 of a cluster per evaluation;
+ *   - at most 6 hull rounds, and at most DP_SHAPES_H_MAX hull vertices per cluster.  A cluster that
+ *     is not down to one chunk by then (its hull has more vertices, or shrinks too slowly) gets error
+ *     flag 1, kind 0, an empty hull range and every other column but the count 0: nothing is fitted
+ *     from a truncated hull.  Other clusters of the call are not affected.
+ * Out of scope: detect_and_split_l_shapes (:79-282), a chain of OpenCV morphology and
+ * connected-components calls on a per-rectangle grid; its input is the rectangle list produced here.
+ * circularity_threshold NaN, max_clusters < 0 or n_max < 0: DP_ERR_SHAPE.
+ */
+#define DP_SHAPES_H_MAX 2048
+int64_t dp_shapes_workspace_size(int64_t n_max, int64_t max_clusters);
+int dp_cluster_shapes(const double* points, const int32_t* n_dev, int32_t n_max, const uint32_t* order,
+                      const int32_t* offsets, const int32_t* n_clusters_dev, int32_t max_clusters,
+                      double circularity_threshold, double* shapes_out, int32_t* hull_rows_out,
+                      int32_t* hull_offsets_out, void* workspace, int64_t workspace_bytes, dp_stream_t stream);
 
 #ifdef __cplusplus
 }

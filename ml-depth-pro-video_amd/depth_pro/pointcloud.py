@@ -20,6 +20,9 @@ Cleaning (the reference pipeline's next step, `pointcloud_cleaner.py:142-309`): 
 Clustering (the per-point part of the floor-plan step, `simple_pointcloud_viewer.py:332-412`):
 `dbscan_labels` (sklearn's DBSCAN labels over (x, z), exactly), `cluster_table`, `cluster_pointcloud`
 and the host-side `cluster_summary` -- csrc/dp_cluster.hip, no sklearn, no host read-back.
+`fit_shapes` / `cluster_shapes` fit each cluster's convex hull, minimum-area rectangle and circle and take
+the reference's circle-or-rectangle decision (csrc/dp_shapes.hip, no scipy, no OpenCV); `shape_summary` and
+`export_shape_text` are their host-side writers.
 """
 
 from __future__ import annotations
@@ -629,6 +632,127 @@ def cluster_summary(table_host, stats_host, params: Optional[dict] = None) -> di
     out["clusters_listed"] = len(clusters)
     out["cluster_table"] = clusters
     return out
+
+
+# ---- cluster shapes: hull, minimum-area rectangle, circle, decision (csrc/dp_shapes.hip) ------------
+
+SHAPE_COLUMNS = ("kind", "count", "rect_cu", "rect_cv", "width", "height", "angle", "area", "xc", "yc", "r", "fit_error",
+                 "hull_area", "hull_vertices", "circ", "error")
+SHAPE_SKIPPED, SHAPE_RECTANGLE, SHAPE_CIRCLE = 0, 1, 2
+
+
+def fit_shapes(points: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor, n_clusters: torch.Tensor, count=None,
+               max_clusters: int = 4096, circularity_threshold: float = 0.85
+               ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """`dp_cluster_shapes` on the `order` / `offsets` / cluster count of `cluster_table` (same
+    `max_clusters`): per cluster the convex hull, the minimum-area rectangle, the least-squares circle
+    and the reference's circle-or-rectangle decision, in the top-down frame u = -x, v = z.  Returns
+    (shapes (max_clusters, 16) float64 in `SHAPE_COLUMNS` order, hull_rows (N,) int32, hull_offsets
+    (max_clusters + 1,) int32): with K = min(n_clusters, max_clusters), rows c < K of the table are
+    written and cluster c's hull vertices are rows `hull_rows[hull_offsets[c]:hull_offsets[c + 1]]`,
+    counter-clockwise from the smallest (u, v).  On the device, asynchronous, no read-back."""
+    mc = int(max_clusters)
+    if mc < 0:
+        raise ValueError(f"max_clusters must be >= 0 (got {max_clusters})")
+    if np.isnan(float(circularity_threshold)):
+        raise ValueError("circularity_threshold must not be NaN")
+    lib, pts, n, count, cptr, stream = _cluster_args(points, count)
+    for t in (order, offsets, n_clusters):
+        if not torch.is_tensor(t) or t.device != pts.device:
+            raise _lib.DPError("order, offsets and n_clusters must be on the points' device")
+    if order.dtype != torch.int32 or tuple(order.shape) != (n,) or not order.is_contiguous():
+        raise ValueError("order must be a contiguous (N,) int32 tensor")
+    if offsets.dtype != torch.int32 or tuple(offsets.shape) != (mc + 1,) or not offsets.is_contiguous():
+        raise ValueError("offsets must be a contiguous (max_clusters + 1,) int32 tensor")
+    if n_clusters.dtype != torch.int32 or n_clusters.numel() != 1:
+        raise ValueError("n_clusters must be a device int32 scalar")
+    ws = torch.empty(int(lib.dp_shapes_workspace_size(n, mc)), dtype=torch.uint8, device=pts.device)
+    shapes = torch.zeros(mc, 16, dtype=torch.float64, device=pts.device)
+    hull_rows = torch.empty(n, dtype=torch.int32, device=pts.device)
+    hull_offsets = torch.zeros(mc + 1, dtype=torch.int32, device=pts.device)
+    check(lib.dp_cluster_shapes(pts.data_ptr(), cptr, n, order.data_ptr(), offsets.data_ptr(), n_clusters.data_ptr(), mc,
+                                float(circularity_threshold), shapes.data_ptr(), hull_rows.data_ptr(),
+                                hull_offsets.data_ptr(), ws.data_ptr(), ws.numel(), stream), "dp_cluster_shapes")
+    return shapes, hull_rows, hull_offsets
+
+
+def cluster_shapes(points: torch.Tensor, count=None, eps: float = 0.2, min_samples: int = 5,
+                   height_threshold: Optional[float] = 1.3, max_points: int = 100000, max_clusters: int = 4096,
+                   circularity_threshold: float = 0.85):
+    """`cluster_pointcloud` then `fit_shapes`, with the reference's `fit_shapes_to_clusters` defaults.
+    Returns `cluster_pointcloud`'s six tensors followed by (shapes, hull_rows, hull_offsets), all on
+    the device, nothing synchronised."""
+    labels, ncl, stats, table, order, offsets = cluster_pointcloud(points, count, eps, min_samples, height_threshold,
+                                                                   max_points, max_clusters)
+    return (labels, ncl, stats, table, order, offsets) + fit_shapes(points, order, offsets, ncl, count, max_clusters,
+                                                                    circularity_threshold)
+
+
+def split_large_rectangle(cu: float, cv: float, width: float, height: float, angle: float):
+    """The reference's forced split of a very large rectangle (simple_pointcloud_viewer.py:284-330):
+    two halves along the longer side.  Pure arithmetic on one rectangle."""
+    a = angle * np.pi / 180.0
+    if width > height:
+        d = width / 4
+        return [(cu - d * np.cos(a), cv - d * np.sin(a), width / 2, height, angle),
+                (cu + d * np.cos(a), cv + d * np.sin(a), width / 2, height, angle)]
+    d = height / 4
+    return [(cu - d * np.sin(a), cv + d * np.cos(a), width, height / 2, angle),
+            (cu + d * np.sin(a), cv - d * np.cos(a), width, height / 2, angle)]
+
+
+def shape_summary(shapes_host, params: Optional[dict] = None) -> dict:
+    """The `{base}_shapes.json` content from the (K, 16) rows of `fit_shapes` already on the host:
+    parameters, counts, and the `rectangles` and `circles` lists in cluster order, as the reference's
+    `fit_shapes_to_clusters` builds them -- a rectangle with width * height > 100 and more than 1000
+    members is split in two (`split_large_rectangle`), each half marked `"split": true`.
+    `detect_and_split_l_shapes` is not applied.  Host only."""
+    t = np.asarray(shapes_host, dtype=np.float64).reshape(-1, 16)
+    rects, circles = [], []
+    skipped = errors = 0
+    for c, r in enumerate(t):
+        kind, cnt = int(r[0]), int(r[1])
+        errors += int(r[15] != 0)
+        if kind == SHAPE_CIRCLE:
+            circles.append({"cluster": c, "count": cnt, "center": [float(r[8]), float(r[9])], "radius": float(r[10]),
+                            "fit_error": float(r[11]), "circularity": float(r[14])})
+        elif kind == SHAPE_RECTANGLE:
+            parts = [(float(r[2]), float(r[3]), float(r[4]), float(r[5]), float(r[6]))]
+            split = bool(r[4] * r[5] > 100 and cnt > 1000)
+            if split:
+                parts = [tuple(float(v) for v in q) for q in split_large_rectangle(*parts[0])]
+            for q in parts:
+                rects.append({"cluster": c, "count": cnt, "center": [q[0], q[1]], "width": q[2], "height": q[3],
+                              "angle": q[4], "split": split, "hull_area": float(r[12]), "hull_vertices": int(r[13]),
+                              "circularity": float(r[14])})
+        else:
+            skipped += 1
+    return {"parameters": dict(params or {}), "clusters_listed": len(t), "skipped": skipped, "errors": errors,
+            "rectangles": rects, "circles": circles}
+
+
+def export_shape_text(summary: dict, path: str) -> None:
+    """Write the reference's `export_shape_data` text (simple_pointcloud_viewer.py:414-453), line for
+    line, from a `shape_summary`."""
+    rects, circles = summary["rectangles"], summary["circles"]
+    with open(path, "w") as f:
+        f.write("# Floor Plan Shape Data\n")
+        f.write("# Units: meters\n\n")
+        f.write(f"Total Shapes: {len(rects) + len(circles)}\n")
+        f.write(f"Rectangles: {len(rects)}\n")
+        f.write(f"Circles: {len(circles)}\n\n")
+        total = sum(r["width"] * r["height"] for r in rects) + sum(np.pi * c["radius"] ** 2 for c in circles)
+        f.write(f"Total Area: {total:.2f} square meters\n\n")
+        f.write("# Rectangles\n")
+        f.write("# Format: ID, center_x, center_y, width, height, angle_degrees, area_m2\n")
+        for i, r in enumerate(rects):
+            f.write(f"{i + 1}, {r['center'][0]:.3f}, {r['center'][1]:.3f}, {r['width']:.3f}, {r['height']:.3f}, "
+                    f"{r['angle']:.1f}, {r['width'] * r['height']:.3f}\n")
+        f.write("\n# Circles\n")
+        f.write("# Format: ID, center_x, center_y, radius, area_m2\n")
+        for i, c in enumerate(circles):
+            f.write(f"{len(rects) + i + 1}, {c['center'][0]:.3f}, {c['center'][1]:.3f}, {c['radius']:.3f}, "
+                    f"{np.pi * c['radius'] ** 2:.3f}\n")
 
 
 GROUND_JSON = "ground.json"

@@ -245,19 +245,26 @@ def labels_name(image_path: str) -> str:
     return f"{os.path.splitext(os.path.basename(image_path))[0]}_labels.npy"
 
 
+def shapes_name(image_path: str) -> str:
+    """`{base}_shapes.json` (--fit_shapes); the reference's text export goes to `{base}_shapes.txt` beside it."""
+    return f"{os.path.splitext(os.path.basename(image_path))[0]}_shapes.json"
+
+
 def plan_frames(image_paths, output_dir: str, world: int, rank: int, resume: bool, cleaned: bool = False,
-                clustered: bool = False) -> List[int]:
+                clustered: bool = False, shaped: bool = False) -> List[int]:
     """Indices of the frames this rank processes: the frames still to do (all of them, or with
     `resume` those whose output file is missing -- decided by rank 0 alone and broadcast before
     any rank writes, so every rank shards the same list), dealt round-robin over the ranks.
     `cleaned` (--clean_pointcloud): a frame also counts as missing without its `{base}_clean.ply`;
-    `clustered` (--cluster_pointcloud): and without its `{base}_clusters.json`."""
+    `clustered` (--cluster_pointcloud): and without its `{base}_clusters.json`; `shaped` (--fit_shapes): and
+    without its `{base}_shapes.json`."""
     todo = list(range(len(image_paths)))
     if resume:
         if rank == 0:
             done = lambda k: os.path.exists(os.path.join(output_dir, output_name(image_paths[k]))) and (   # noqa: E731
                 not cleaned or os.path.exists(os.path.join(output_dir, cloud_name(image_paths[k], True)))) and (
-                not clustered or os.path.exists(os.path.join(output_dir, clusters_name(image_paths[k]))))
+                not clustered or os.path.exists(os.path.join(output_dir, clusters_name(image_paths[k])))) and (
+                not shaped or os.path.exists(os.path.join(output_dir, shapes_name(image_paths[k]))))
             todo = [k for k in todo if not done(k)]
         if world > 1:
             box = [todo]
@@ -271,7 +278,8 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                               resume=False, model=None, normalize_ground=False, ground_params_dir=None, grid_size=20,
                               ground_percentile=5, rotation_offset=None, clean_pointcloud=False, stray_radius=0.1,
                               stray_neighbors=20, cluster_pointcloud=False, cluster_eps=0.2, cluster_min_samples=5,
-                              cluster_height=1.3, cluster_max_points=100000):
+                              cluster_height=1.3, cluster_max_points=100000, fit_shapes=False,
+                              circularity_threshold=0.85):
     """Directory loop (reference :153-206), pipelined decode -> GPU -> encode, frame-sharded across ranks.
 
     Every rank writes its own frames' files; each frame has exactly one owner.  resume=True skips
@@ -297,12 +305,21 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
     cluster_max_points, 0 = all) and writes `{base}_clusters.json` (parameters, counts, per-cluster count,
     bounding box, centroid, smallest core row) and `{base}_labels.npy` (int32, in the row order of
     `{base}_clean.ply`) beside the cloud; queued on the frame's stream like every other output.
+    fit_shapes=True (implies cluster_pointcloud) fits each cluster's convex hull, minimum-area rectangle
+    and circle on the same stream right after the cluster table (`PC.fit_shapes`, with the reference's
+    circle-or-rectangle decision at circularity_threshold) and writes `{base}_shapes.json`
+    (`PC.shape_summary`) and `{base}_shapes.txt` (the reference's `export_shape_data` layout).
     `model`: an already-built (model, transform) pair (tests); default: `_model`.
     Returns the number of frames this rank wrote.
     """
     ground = None
     clean = None
     cluster = None
+    shapes = None
+    if fit_shapes:
+        check_circularity(circularity_threshold)
+        cluster_pointcloud = True
+        shapes = {"circularity_threshold": float(circularity_threshold)}
     if cluster_pointcloud:
         check_cluster(cluster_eps, cluster_min_samples, cluster_max_points)
         clean_pointcloud = True
@@ -326,7 +343,7 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
     if ground is not None:
         ground["world"], ground["rank"] = world, rank
     mine = plan_frames(image_paths, output_dir, world, rank, resume, cleaned=clean is not None,
-                       clustered=cluster is not None)
+                       clustered=cluster is not None, shaped=shapes is not None)
     print(f"[rank {rank}/{world}] Found {len(image_paths)} images, processing {len(mine)}")
     if model is None:
         model = _model(_device(), half_precision)
@@ -383,7 +400,7 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                     host = _image_async(depth, colored, cmap)
                     gpu_img = True
                     if pointcloud:
-                        pc = _points(depth, pred["focallength_px"], image, ground, image_paths[k], clean, cluster)
+                        pc = _points(depth, pred["focallength_px"], image, ground, image_paths[k], clean, cluster, shapes)
                     ev = torch.cuda.Event()
                     ev.record()
                 else:
@@ -392,7 +409,8 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                 def _finish(host=host, ev=ev, path=output_path, pc=pc, status=status, gpu_img=gpu_img,
                             cloud=os.path.join(output_dir, cloud_name(image_paths[k], clean is not None)),
                             cjson=os.path.join(output_dir, clusters_name(image_paths[k])),
-                            cnpy=os.path.join(output_dir, labels_name(image_paths[k]))):
+                            cnpy=os.path.join(output_dir, labels_name(image_paths[k])),
+                            sjson=os.path.join(output_dir, shapes_name(image_paths[k]))):
                     if ev is not None:
                         ev.synchronize()
                     if status is not None:
@@ -401,6 +419,8 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                         PC.write_ply_records(cloud, _points_host(pc))
                         if cluster is not None:
                             _write_clusters(pc, cluster, cjson, cnpy)
+                        if shapes is not None:
+                            _write_shapes(pc, cluster, shapes, sjson)
                     if gpu_img:
                         _write_png(path, _host_image(host))
                         return path
@@ -445,6 +465,11 @@ def check_cluster(eps, min_samples, max_points) -> None:
         raise ValueError(f"--cluster_max_points must be >= 0 (got {max_points})")
 
 
+def check_circularity(threshold) -> None:
+    if np.isnan(float(threshold)):
+        raise ValueError("--circularity_threshold must not be nan")
+
+
 MAX_CLUSTERS = 4096     # rows of the per-frame cluster table (a frame with more lists the first 4096)
 
 
@@ -483,7 +508,7 @@ def _ground_plane(ground: dict, xyz, count, image_path):
     return model
 
 
-def _points(depth: torch.Tensor, f_px, image, ground=None, image_path=None, clean=None, cluster=None):
+def _points(depth: torch.Tensor, f_px, image, ground=None, image_path=None, clean=None, cluster=None, shapes=None):
     """Queue the frame's point cloud on the GPU (depth_to_3d, img_to_normalized_pointcloud.py:819-856),
     interleaved into PLY vertex records there, and their copy into a pinned host buffer, on the
     current stream, without a host synchronisation: the full-size record buffer + the point count
@@ -507,8 +532,11 @@ def _points(depth: torch.Tensor, f_px, image, ground=None, image_path=None, clea
     extra = ()
     if cluster is not None:
         # clusters of the cleaned cloud (--cluster_pointcloud): labels, table and counts, same stream, no sync
-        labels, ncl, stats, table, _, _ = PC.cluster_pointcloud(xyz, count, max_clusters=MAX_CLUSTERS, **cluster)
+        labels, ncl, stats, table, order, offsets = PC.cluster_pointcloud(xyz, count, max_clusters=MAX_CLUSTERS, **cluster)
         extra = (labels, ncl, stats, table)
+        if shapes is not None:
+            # the clusters' shapes (--fit_shapes): queued right behind the table; only the small table goes to the host
+            extra += (PC.fit_shapes(xyz, order, offsets, ncl, count, MAX_CLUSTERS, shapes["circularity_threshold"])[0],)
     out = []
     for t in (PC.ply_records_async(xyz, cols), count) + extra:
         hbuf = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
@@ -527,12 +555,24 @@ def _write_clusters(pc, cluster: dict, json_path: str, npy_path: str) -> None:
     """Writer-thread side: `{base}_labels.npy` (the live rows' labels) and `{base}_clusters.json`."""
     import json
 
-    n, (labels, ncl, stats, table) = int(pc[1]), pc[2:]
+    n, (labels, ncl, stats, table) = int(pc[1]), pc[2:6]
     np.save(npy_path, labels[:n].numpy())
     k = min(int(ncl), MAX_CLUSTERS)
     with open(json_path, "w") as f:
         params = {key: (None if isinstance(v, float) and v != v else v) for key, v in cluster.items()}   # NaN height
         json.dump(PC.cluster_summary(table[:k].numpy(), stats.numpy(), params), f, indent=1)
+
+
+def _write_shapes(pc, cluster: dict, shapes: dict, json_path: str) -> None:
+    """Writer-thread side: `{base}_shapes.json` and `{base}_shapes.txt`."""
+    import json
+
+    k = min(int(pc[3]), MAX_CLUSTERS)
+    params = {key: (None if isinstance(v, float) and v != v else v) for key, v in {**cluster, **shapes}.items()}
+    summary = PC.shape_summary(pc[6][:k].numpy(), params)
+    with open(json_path, "w") as f:
+        json.dump(summary, f, indent=1)
+    PC.export_shape_text(summary, os.path.splitext(json_path)[0] + ".txt")
 
 
 def main():
@@ -575,9 +615,15 @@ def main():
                         help="Cluster the points with y >= this height in metres (default 1.3; nan: every height)")
     parser.add_argument("--cluster_max_points", type=int, default=100000,
                         help="Cluster at most this many points, an even stride of the rest (default 100000; 0: all)")
+    parser.add_argument("--fit_shapes", action="store_true",
+                        help="Fit a rectangle or a circle to every cluster (implies --cluster_pointcloud): "
+                             "{frame}_shapes.json and the floor-plan text {frame}_shapes.txt")
+    parser.add_argument("--circularity_threshold", type=float, default=0.85,
+                        help="Hull area over circle area above which a cluster may be a circle (default 0.85)")
     parser.add_argument("--resume", action="store_true",
                         help="Skip frames whose {frame}_depth.png (with --clean_pointcloud: and {frame}_clean.ply; with "
-                             "--cluster_pointcloud: and {frame}_clusters.json) already exists in --output_dir")
+                             "--cluster_pointcloud: and {frame}_clusters.json; with --fit_shapes: and {frame}_shapes.json) already "
+                             "exists in --output_dir")
     parser.add_argument("--colormap", type=str, default="turbo",
                         choices=["turbo", "viridis", "plasma", "inferno", "magma", "cividis", "jet"],
                         help="Colormap for depth visualization")
@@ -589,6 +635,7 @@ def main():
     try:
         check_stray(args.stray_radius, args.stray_neighbors)
         check_cluster(args.cluster_eps, args.cluster_min_samples, args.cluster_max_points)
+        check_circularity(args.circularity_threshold)
     except ValueError as e:
         parser.error(str(e))
     batch_generate_depth_maps(input_dir=args.input_dir, output_dir=args.output_dir, pattern=args.pattern,
@@ -601,7 +648,8 @@ def main():
                               clean_pointcloud=args.clean_pointcloud, stray_radius=args.stray_radius,
                               stray_neighbors=args.stray_neighbors, cluster_pointcloud=args.cluster_pointcloud,
                               cluster_eps=args.cluster_eps, cluster_min_samples=args.cluster_min_samples,
-                              cluster_height=args.cluster_height, cluster_max_points=args.cluster_max_points)
+                              cluster_height=args.cluster_height, cluster_max_points=args.cluster_max_points,
+                              fit_shapes=args.fit_shapes, circularity_threshold=args.circularity_threshold)
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()

@@ -40,6 +40,10 @@ def main():
                     help="level the point clouds (--normalize_ground of the loop; implies --pointcloud)")
     ap.add_argument("--clean-pointcloud", action="store_true",
                     help="clean the levelled clouds (--clean_pointcloud of the loop; implies --normalize-ground)")
+    ap.add_argument("--cluster-pointcloud", action="store_true",
+                    help="cluster the cleaned clouds (--cluster_pointcloud of the loop; implies --clean-pointcloud)")
+    ap.add_argument("--fit-shapes", action="store_true",
+                    help="fit the clusters' shapes (--fit_shapes of the loop; implies --cluster-pointcloud)")
     ap.add_argument("--raw", action="store_true")
     ap.add_argument("--workers", type=int, default=None,
                     help="decode and encode threads each (default: the loop's own defaults)")
@@ -126,6 +130,10 @@ def main():
     m, transform = model
     torch.cuda.synchronize()
     t_setup = time.time() - t
+    if args.fit_shapes:
+        args.cluster_pointcloud = True
+    if args.cluster_pointcloud:
+        args.clean_pointcloud = True
     if args.clean_pointcloud:
         args.normalize_ground = True
     if args.normalize_ground:
@@ -135,6 +143,10 @@ def main():
         kw["normalize_ground"] = True
     if args.clean_pointcloud:
         kw["clean_pointcloud"] = True
+    if args.cluster_pointcloud:
+        kw["cluster_pointcloud"] = True
+    if args.fit_shapes:
+        kw["fit_shapes"] = True
     if args.workers:
         kw.update(decode_workers=args.workers, encode_workers=args.workers)
     import inspect
@@ -220,7 +232,8 @@ def main():
     out = {
         "what": "generate_depth_maps.batch_generate_depth_maps end to end, 1 GPU",
         "frames": args.frames, "size": [W, H], "pointcloud": args.pointcloud, "normalize_ground": args.normalize_ground,
-        "clean_pointcloud": args.clean_pointcloud,
+        "clean_pointcloud": args.clean_pointcloud, "cluster_pointcloud": args.cluster_pointcloud,
+        "fit_shapes": args.fit_shapes,
         "raw": args.raw,
         "ply_records": "host (numpy)" if args.ply_host else "GPU",
         "png_writer": "bytes copies" if args.png_copy else "zero-copy parts",

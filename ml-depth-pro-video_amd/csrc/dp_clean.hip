@@ -4,16 +4,15 @@
 // so each product and sum is rounded on its own.  Three kernels per sort pass (histogram, table
 // scan, scatter); no kernel waits on another workgroup's progress.
 #include "dp_common.h"
+#include "dp_points.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-typedef unsigned long long u64;
+constexpr int GRID_CAP = 4096;                  // workgroups of a per-point kernel at the most
 constexpr int SORT_ITEMS = 16;                  // rounds of 256 consecutive elements per workgroup
 constexpr int SORT_TILE = 256 * SORT_ITEMS;     // elements of one workgroup (sort)
-constexpr int CMP_ITEMS = 8;
-constexpr int CMP_TILE = 256 * CMP_ITEMS;       // elements of one workgroup (compaction)
 constexpr int CELL_BITS = 21;                   // stray grid: bits per axis of the packed cell key
 constexpr int CELL_MAX = (1 << CELL_BITS) - 2;  // largest cell coordinate (its +1 neighbour still fits)
 constexpr uint32_t NO_COL = 0xffffffffu;        // shadow stage: "in no column"
@@ -27,31 +26,6 @@ struct Hdr {
 enum { C_FINITE = 0, C_NONFINITE = 1, C_KEPT = 2, C_ERR = 3, C_OCC = 4, C_TESTED = 5, C_REMCOL = 6, C_REMPTS = 7,
        C_LENX = 8, C_LENZ = 9 };
 
-// fp64 -> order-preserving u64 (-0.0 folded onto +0.0): dp_seg_select's mapping
-__device__ __forceinline__ u64 okey(double x) {
-  u64 b = (u64)__double_as_longlong(x);
-  if (x == 0.0) b = 0;
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double unkey(u64 k) {
-  const u64 b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-  return __longlong_as_double((long long)b);
-}
-__device__ __forceinline__ bool fin(double v) { return __builtin_fabs(v) < __builtin_inf(); }
-__device__ __forceinline__ bool finite3(double x, double y, double z) { return fin(x) && fin(y) && fin(z); }
-
-__device__ __forceinline__ int live_n(const int32_t* n_dev, int n_max) {
-  int n = n_dev ? *n_dev : n_max;
-  n = n < 0 ? 0 : n;
-  return n < n_max ? n : n_max;
-}
-__device__ __forceinline__ void wave_count(uint32_t* c, bool p) {
-  const u64 m = __ballot(p);
-  if ((threadIdx.x & 63) == 0 && m) atomicAdd(c, (uint32_t)__popcll(m));
-}
-// A payload of the sort is a row index below n by construction; the clamp only keeps a read inside
-// the array whatever the buffers hold.
-__device__ __forceinline__ size_t row_of(uint32_t v, int n) { return v < (uint32_t)n ? v : (uint32_t)(n - 1); }
 __device__ __forceinline__ u64 lanes_below() { return (1ull << (threadIdx.x & 63)) - 1ull; }
 
 // Lanes of the wave that hold the same 8-bit digit as this one (64-lane ballots, one per bit);
@@ -65,28 +39,6 @@ __device__ __forceinline__ u64 match_digit(bool valid, uint32_t d) {
     peers &= bit ? bb : ~bb;
   }
   return peers;
-}
-
-// exclusive scan over the 256 threads of the workgroup (wsum: 4 shared words)
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* wsum, uint32_t* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint32_t inc = v;
-  #pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = __shfl_up(inc, o);
-    if (lane >= o) inc += t;
-  }
-  if (lane == 63) wsum[w] = inc;
-  __syncthreads();
-  uint32_t pre = 0, tot = 0;
-  for (int k = 0; k < 4; ++k) {
-    const uint32_t s = wsum[k];
-    if (k < w) pre += s;
-    tot += s;
-  }
-  __syncthreads();
-  if (total) *total = tot;
-  return pre + inc - v;
 }
 
 // ---- the sort -----------------------------------------------------------------------------------
@@ -126,7 +78,7 @@ __global__ void __launch_bounds__(256) sort_scan_kernel(uint32_t* __restrict__ t
   const long long b1 = b0 + per < nblocks ? b0 + per : nblocks;
   uint32_t s = 0;
   for (long long b = b0; b < b1; ++b) s += row[b];
-  uint32_t run = dbase + block_excl_scan(s, wsum, nullptr);
+  uint32_t run = dbase + block_excl_scan(s, wsum);
   for (long long b = b0; b < b1; ++b) {
     const uint32_t t = row[b];
     row[b] = run;
@@ -183,10 +135,6 @@ __global__ void __launch_bounds__(256) copy_pairs_kernel(const u64* __restrict__
   }
 }
 
-int grid_for(int n_max) {
-  long long g = ((long long)n_max + 255) / 256;
-  return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
-}
 int sort_blocks(int64_t n_max) { return (int)((n_max + SORT_TILE - 1) / SORT_TILE); }
 int sort_passes(int bit_lo, int bit_hi) {
   int p = 0;
@@ -224,7 +172,6 @@ struct Ws {
   uint32_t *va, *vb, *table;
   char* aux;            // 24 n bytes: sorted coordinates (stray) / per-column extremes and run heads (shadows)
 };
-int64_t al256(int64_t b) { return (b + 255) / 256 * 256; }
 int64_t ws_bytes_for(int64_t n_max) {
   const int64_t n = n_max < 0 ? 0 : n_max;
   return al256(sizeof(Hdr)) + 2 * al256(8 * n) + 2 * al256(4 * n) + al256((int64_t)sort_blocks(n) * 1024) +
@@ -264,18 +211,13 @@ __global__ void __launch_bounds__(256) minmax3_kernel(const double* __restrict__
   }
   #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
-    #pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const u64 t0 = __shfl_xor(mn[a], o), t1 = __shfl_xor(mx[a], o);
-      mn[a] = t0 < mn[a] ? t0 : mn[a];
-      mx[a] = t1 > mx[a] ? t1 : mx[a];
-    }
+    wave_minmax(mn, mx, o);
     bad += __shfl_xor(bad, o);
     good += __shfl_xor(good, o);
   }
   if ((threadIdx.x & 63) == 0) {
     if (good) {
-      for (int a = 0; a < 3; ++a) { atomicMin(&h->mm[2 * a], mn[a]); atomicMax(&h->mm[2 * a + 1], mx[a]); }
+      flush_minmax(h->mm, mn, mx);
       atomicAdd(&h->ctr[C_FINITE], good);
     }
     if (bad) atomicAdd(&h->ctr[C_NONFINITE], bad);
@@ -301,10 +243,6 @@ __global__ void stray_setup_kernel(Hdr* h, double radius) {
   h->ctr[C_ERR] = err;
 }
 
-__device__ __forceinline__ u64 cell_of(double v, double mn, double edge) {
-  const double q = __builtin_floor((v - mn) / edge);
-  return (u64)(q < 0.0 ? 0.0 : (q > (double)CELL_MAX ? (double)CELL_MAX : q));
-}
 __device__ __forceinline__ u64 pack_cell(u64 cx, u64 cy, u64 cz) { return (cx << (2 * CELL_BITS)) | (cy << CELL_BITS) | cz; }
 
 __global__ void __launch_bounds__(256) stray_key_kernel(const double* __restrict__ pts, const int32_t* n_dev, int n_max,
@@ -313,7 +251,9 @@ __global__ void __launch_bounds__(256) stray_key_kernel(const double* __restrict
   const double mx = h->par[0], my = h->par[1], mz = h->par[2], edge = h->par[3];
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
     const double x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
-    keys[i] = finite3(x, y, z) ? pack_cell(cell_of(x, mx, edge), cell_of(y, my, edge), cell_of(z, mz, edge)) : ~0ull;
+    keys[i] = finite3(x, y, z) ? pack_cell(cell_of<CELL_MAX>(x, mx, edge), cell_of<CELL_MAX>(y, my, edge),
+                                           cell_of<CELL_MAX>(z, mz, edge))
+                               : ~0ull;
     vals[i] = (uint32_t)i;
   }
 }
@@ -325,16 +265,6 @@ __global__ void __launch_bounds__(256) gather_points_kernel(const double* __rest
     const size_t i = row_of(idx[t], n);
     out[3 * t] = pts[3 * i]; out[3 * t + 1] = pts[3 * i + 1]; out[3 * t + 2] = pts[3 * i + 2];
   }
-}
-
-// first position in keys[0, n) with keys[pos] >= k
-__device__ __forceinline__ int lower_bound(const u64* __restrict__ keys, int n, u64 k) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (keys[mid] < k) lo = mid + 1; else hi = mid;
-  }
-  return lo;
 }
 
 // One thread per point, in sorted (cell) order.  Own (x, y) cell row first; every row's three
@@ -547,7 +477,7 @@ __global__ void __launch_bounds__(256) shadow_decide_kernel(const double* __rest
       is_head = col != NO_COL && (t == 0 || keys[t - 1] != col);
       if (is_head) {
         count = (uint32_t)(lower_bound(keys, n, col + 1) - (int)t);
-        const double y0 = pts[3 * row_of(idx[t], n) + 1], y1 = pts[3 * row_of(idx[t + count - 1], n) + 1];
+        const double y0 = pts[3 * (size_t)row_of(idx[t], n) + 1], y1 = pts[3 * (size_t)row_of(idx[t + count - 1], n) + 1];
         tested = count >= (uint32_t)min_pts && count >= 3 && (y1 - y0) > height_thr;
         if (tested) {
           const uint32_t raw = cnt[t], c = raw & 0x7fffffffu, m = count - 1;
@@ -587,47 +517,16 @@ __global__ void shadow_final_kernel(const Hdr* h, double* st) {
 }
 
 // ---- compaction ---------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) compact_count_kernel(const uint8_t* __restrict__ keep, const int32_t* n_dev,
-                                                            int n_max, uint32_t* __restrict__ bc) {
-  __shared__ uint32_t wsum[4];
-  const int n = live_n(n_dev, n_max);
-  const long long tile = (long long)blockIdx.x * CMP_TILE;
-  uint32_t c = 0;
-  for (int r = 0; r < CMP_ITEMS; ++r) {
-    const long long i = tile + r * 256 + threadIdx.x;
-    c += i < n && keep[i];
-  }
-  uint32_t tot = 0;
-  block_excl_scan(c, wsum, &tot);
-  if (threadIdx.x == 0) bc[blockIdx.x] = tot;
-}
-
-// one workgroup: block counts -> exclusive offsets, total -> *n_out
-__global__ void __launch_bounds__(256) compact_scan_kernel(uint32_t* __restrict__ bc, int nblocks, int32_t* n_out) {
-  __shared__ uint32_t wsum[4];
-  const int per = (nblocks + 255) / 256;
-  const long long b0 = (long long)threadIdx.x * per;
-  const long long b1 = b0 + per < nblocks ? b0 + per : nblocks;
-  uint32_t s = 0, tot = 0;
-  for (long long b = b0; b < b1; ++b) s += bc[b];
-  uint32_t run = block_excl_scan(s, wsum, &tot);
-  for (long long b = b0; b < b1; ++b) {
-    const uint32_t t = bc[b];
-    bc[b] = run;
-    run += t;
-  }
-  if (threadIdx.x == 0) *n_out = (int32_t)tot;
-}
-
+// the flags' scan is scan_count_kernel and scan_blocks_kernel (dp_points.h); this moves the rows
 __global__ void __launch_bounds__(256) compact_scatter_kernel(const double* __restrict__ pts, const uint8_t* __restrict__ cols,
                                                               const uint8_t* __restrict__ keep, const int32_t* n_dev,
                                                               int n_max, const uint32_t* __restrict__ bc,
                                                               double* __restrict__ pts_out, uint8_t* __restrict__ cols_out) {
   __shared__ uint32_t wsum[4];
   const int n = live_n(n_dev, n_max);
-  const long long tile = (long long)blockIdx.x * CMP_TILE;
+  const long long tile = (long long)blockIdx.x * SCAN_TILE;
   uint32_t run = bc[blockIdx.x];
-  for (int r = 0; r < CMP_ITEMS && tile + r * 256 < n; ++r) {
+  for (int r = 0; r < SCAN_ITEMS && tile + r * 256 < n; ++r) {
     const long long i = tile + r * 256 + threadIdx.x;
     const bool k = i < n && keep[i];
     uint32_t tot = 0;
@@ -655,8 +554,8 @@ extern "C" int dp_sort_pairs(uint64_t* keys, uint32_t* values, const int32_t* n_
   if (!ws_carve(workspace, workspace_bytes, n_max, &w)) return DP_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   if (run_sort(s, w.h, (u64*)keys, values, w.kb, w.vb, w.table, n_dev, n_max, bit_lo, bit_hi))
-    hipLaunchKernelGGL(copy_pairs_kernel, dim3(grid_for(n_max)), dim3(256), 0, s, w.kb, w.vb, (u64*)keys, values, n_dev,
-                       n_max);
+    hipLaunchKernelGGL(copy_pairs_kernel, dim3(grid_for(n_max, GRID_CAP)), dim3(256), 0, s, w.kb, w.vb, (u64*)keys, values,
+                       n_dev, n_max);
   DP_CHECK_LAUNCH();
   return 0;
 }
@@ -669,7 +568,7 @@ extern "C" int dp_clean_stray(const double* points, const int32_t* n_dev, int32_
   Ws w;
   if (!ws_carve(workspace, workspace_bytes, n_max, &w)) return DP_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const int g = grid_for(n_max);
+  const int g = grid_for(n_max, GRID_CAP);
   double* sp = (double*)w.aux;
   (void)hipMemsetAsync(w.h, 0, sizeof(Hdr), s);
   hipLaunchKernelGGL(hdr_init_kernel, dim3(1), dim3(1), 0, s, w.h);
@@ -695,7 +594,7 @@ extern "C" int dp_clean_shadows(const double* points, const int32_t* n_dev, int3
   Ws w;
   if (!ws_carve(workspace, workspace_bytes, n_max, &w)) return DP_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const int g = grid_for(n_max);
+  const int g = grid_for(n_max, GRID_CAP);
   u64* amin = (u64*)w.aux;                                        // aux: 8 n + 4 n of its 24 n bytes
   uint32_t* head_of = (uint32_t*)(w.aux + al256(8 * (int64_t)n_max));
   (void)hipMemsetAsync(w.h, 0, sizeof(Hdr), s);
@@ -729,10 +628,10 @@ extern "C" int dp_compact_points(const double* points, const uint8_t* colors, co
   Ws w;
   if (!ws_carve(workspace, workspace_bytes, n_max, &w)) return DP_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const int nb = (int)(((int64_t)n_max + CMP_TILE - 1) / CMP_TILE);
+  const int nb = (int)(((int64_t)n_max + SCAN_TILE - 1) / SCAN_TILE);
   uint32_t* bc = w.va;                                            // n / 2048 words
-  if (nb) hipLaunchKernelGGL(compact_count_kernel, dim3(nb), dim3(256), 0, s, keep, n_dev, n_max, bc);
-  hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(256), 0, s, bc, nb, n_out_dev);
+  if (nb) hipLaunchKernelGGL(scan_count_kernel, dim3(nb), dim3(256), 0, s, keep, n_dev, n_max, bc);
+  hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(256), 0, s, bc, nb, (uint32_t*)n_out_dev);   // the same bits
   if (nb)
     hipLaunchKernelGGL(compact_scatter_kernel, dim3(nb), dim3(256), 0, s, points, colors, keep, n_dev, n_max, bc, points_out,
                        colors_out);

@@ -7,14 +7,13 @@
 // No kernel waits on another workgroup's progress: union-find retries on its own CAS only, and every
 // per-thread loop runs over the contents of at most 25 cells, never over n_max.
 #include "dp_common.h"
+#include "dp_points.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-typedef unsigned long long u64;
-constexpr int SCAN_ITEMS = 8;
-constexpr int SCAN_TILE = 256 * SCAN_ITEMS;     // rows of one workgroup (scans)
+constexpr int GRID_CAP = 4096;                  // workgroups of a per-point kernel at the most
 constexpr int CELL_BITS = 21;                   // bits per axis of the packed cell key
 constexpr int CELL_MAX = (1 << CELL_BITS) - 3;  // largest cell coordinate (its +2 neighbour still fits)
 constexpr u64 NO_CELL = 1ull << (2 * CELL_BITS);   // key of a row that takes no part: sorts last
@@ -30,96 +29,8 @@ struct CHdr {
 enum { C_FINITE = 0, C_NONFINITE = 1, C_ELIG = 2, C_PART = 3, C_CORE = 4, C_BORDER = 5, C_NCL = 6, C_ERR = 7,
        C_NP = 8 };
 
-// fp64 -> order-preserving u64 (-0.0 folded onto +0.0): dp_seg_select's mapping
-__device__ __forceinline__ u64 okey(double x) {
-  u64 b = (u64)__double_as_longlong(x);
-  if (x == 0.0) b = 0;
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double unkey(u64 k) {
-  const u64 b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-  return __longlong_as_double((long long)b);
-}
-__device__ __forceinline__ bool fin(double v) { return __builtin_fabs(v) < __builtin_inf(); }
-
-__device__ __forceinline__ int live_n(const int32_t* n_dev, int n_max) {
-  int n = n_dev ? *n_dev : n_max;
-  n = n < 0 ? 0 : n;
-  return n < n_max ? n : n_max;
-}
-__device__ __forceinline__ void wave_count(uint32_t* c, bool p) {
-  const u64 m = __ballot(p);
-  if ((threadIdx.x & 63) == 0 && m) atomicAdd(c, (uint32_t)__popcll(m));
-}
-// A payload of the sort is a row index below n by construction; the clamp only keeps a read inside
-// the array whatever the buffers hold.
-__device__ __forceinline__ uint32_t row_of(uint32_t v, int n) { return v < (uint32_t)n ? v : (uint32_t)(n - 1); }
-
-// exclusive scan over the 256 threads of the workgroup (wsum: 4 shared words)
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* wsum, uint32_t* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint32_t inc = v;
-  #pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = __shfl_up(inc, o);
-    if (lane >= o) inc += t;
-  }
-  if (lane == 63) wsum[w] = inc;
-  __syncthreads();
-  uint32_t pre = 0, tot = 0;
-  for (int k = 0; k < 4; ++k) {
-    const uint32_t s = wsum[k];
-    if (k < w) pre += s;
-    tot += s;
-  }
-  __syncthreads();
-  if (total) *total = tot;
-  return pre + inc - v;
-}
-
-// first position in keys[0, n) with keys[pos] >= k
-__device__ __forceinline__ int lower_bound(const u64* __restrict__ keys, int n, u64 k) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (keys[mid] < k) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
-// ---- exclusive scan of a byte flag in row order (the compaction's pattern: counts, one scan, ranks)
-__global__ void __launch_bounds__(256) scan_count_kernel(const uint8_t* __restrict__ f, const int32_t* n_dev, int n_max,
-                                                         uint32_t* __restrict__ bc) {
-  __shared__ uint32_t wsum[4];
-  const int n = live_n(n_dev, n_max);
-  const long long tile = (long long)blockIdx.x * SCAN_TILE;
-  uint32_t c = 0;
-  for (int r = 0; r < SCAN_ITEMS; ++r) {
-    const long long i = tile + r * 256 + threadIdx.x;
-    c += i < n && f[i];
-  }
-  uint32_t tot = 0;
-  block_excl_scan(c, wsum, &tot);
-  if (threadIdx.x == 0) bc[blockIdx.x] = tot;
-}
-
-// one workgroup: block counts -> exclusive offsets, total -> *tot_out
-__global__ void __launch_bounds__(256) scan_blocks_kernel(uint32_t* __restrict__ bc, int nblocks, uint32_t* tot_out) {
-  __shared__ uint32_t wsum[4];
-  const int per = (nblocks + 255) / 256;
-  const long long b0 = (long long)threadIdx.x * per;
-  const long long b1 = b0 + per < nblocks ? b0 + per : nblocks;
-  uint32_t s = 0, tot = 0;
-  for (long long b = b0; b < b1; ++b) s += bc[b];
-  uint32_t run = block_excl_scan(s, wsum, &tot);
-  for (long long b = b0; b < b1; ++b) {
-    const uint32_t t = bc[b];
-    bc[b] = run;
-    run += t;
-  }
-  if (threadIdx.x == 0) *tot_out = tot;
-}
-
+// ---- exclusive scan of a byte flag in row order: scan_count_kernel, scan_blocks_kernel (dp_points.h),
+// then the ranks
 __global__ void __launch_bounds__(256) scan_write_kernel(const uint8_t* __restrict__ f, const int32_t* n_dev, int n_max,
                                                          const uint32_t* __restrict__ bc, uint32_t* __restrict__ out) {
   __shared__ uint32_t wsum[4];
@@ -190,16 +101,11 @@ __global__ void __launch_bounds__(256) part_kernel(const double* __restrict__ pt
   }
   #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
-    #pragma unroll
-    for (int a = 0; a < 2; ++a) {
-      const u64 t0 = __shfl_xor(mn[a], o), t1 = __shfl_xor(mx[a], o);
-      mn[a] = t0 < mn[a] ? t0 : mn[a];
-      mx[a] = t1 > mx[a] ? t1 : mx[a];
-    }
+    wave_minmax(mn, mx, o);
     cnt += __shfl_xor(cnt, o);
   }
   if ((threadIdx.x & 63) == 0 && cnt) {
-    for (int a = 0; a < 2; ++a) { atomicMin(&h->mm[2 * a], mn[a]); atomicMax(&h->mm[2 * a + 1], mx[a]); }
+    flush_minmax(h->mm, mn, mx);
     atomicAdd(&h->ctr[C_PART], cnt);
   }
 }
@@ -233,10 +139,6 @@ __global__ void setup_kernel(CHdr* h, double eps) {
   h->ctr[C_NP] = err ? 0u : h->ctr[C_PART];
 }
 
-__device__ __forceinline__ u64 cell_of(double v, double mn, double edge) {
-  const double q = __builtin_floor((v - mn) / edge);
-  return (u64)(q < 0.0 ? 0.0 : (q > (double)CELL_MAX ? (double)CELL_MAX : q));
-}
 __device__ __forceinline__ u64 pack_cell(u64 cx, u64 cz) { return (cx << CELL_BITS) | cz; }
 
 __global__ void __launch_bounds__(256) key_kernel(const double* __restrict__ pts, const int32_t* n_dev, int n_max,
@@ -246,7 +148,9 @@ __global__ void __launch_bounds__(256) key_kernel(const double* __restrict__ pts
   const double mx = h->par[0], mz = h->par[1], edge = h->par[2];
   const bool err = h->ctr[C_ERR] != 0;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    keys[i] = part[i] && !err ? pack_cell(cell_of(pts[3 * i], mx, edge), cell_of(pts[3 * i + 2], mz, edge)) : NO_CELL;
+    keys[i] = part[i] && !err
+                  ? pack_cell(cell_of<CELL_MAX>(pts[3 * i], mx, edge), cell_of<CELL_MAX>(pts[3 * i + 2], mz, edge))
+                  : NO_CELL;
     vals[i] = (uint32_t)i;
   }
 }
@@ -466,12 +370,6 @@ __global__ void final_kernel(CHdr* h, int n_max, int32_t* n_clusters, double* st
 }
 
 // ---- the cluster table ----------------------------------------------------------------------------
-__device__ __forceinline__ int table_rows(const int32_t* ncl, int max_clusters) {
-  int k = *ncl;
-  k = k < 0 ? 0 : k;
-  return k < max_clusters ? k : max_clusters;
-}
-
 __global__ void __launch_bounds__(256) tkey_kernel(const int32_t* __restrict__ labels, const int32_t* n_dev, int n_max,
                                                    u64* __restrict__ keys, uint32_t* __restrict__ vals) {
   const int n = live_n(n_dev, n_max);
@@ -549,7 +447,7 @@ __global__ void __launch_bounds__(256) taccum_kernel(const double* __restrict__ 
       }
       if (lane == leader) {
         u64* row = (u64*)(table + 12 * lc);
-        for (int a = 0; a < 3; ++a) { atomicMin(&row[2 + 2 * a], mn[a]); atomicMax(&row[3 + 2 * a], mx[a]); }
+        flush_minmax(row + 2, mn, mx);
         atomicAdd(&table[12 * lc + 8], s[0]);                    // sums: x, y, z
         atomicAdd(&table[12 * lc + 9], s[2]);
         atomicAdd(&table[12 * lc + 10], s[1]);
@@ -572,12 +470,7 @@ __global__ void __launch_bounds__(256) tfinal_kernel(const int32_t* ncl, int max
   }
 }
 
-int grid_for(int64_t n) {
-  const int64_t g = (n + 255) / 256;
-  return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
-}
 int scan_blocks(int64_t n_max) { return (int)((n_max + SCAN_TILE - 1) / SCAN_TILE); }
-int64_t al256(int64_t b) { return (b + 255) / 256 * 256; }
 
 // ---- workspace ----------------------------------------------------------------------------------
 struct Ws {
@@ -638,7 +531,7 @@ extern "C" int dp_cluster_dbscan(const double* points, const int32_t* n_dev, int
   Ws w;
   if (!ws_carve(workspace, workspace_bytes, n_max, &w)) return DP_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const int g = grid_for(n_max);
+  const int g = grid_for(n_max, GRID_CAP);
   const double eps2 = eps * eps;
   (void)hipMemsetAsync(w.h, 0, sizeof(CHdr), s);
   hipLaunchKernelGGL(hdr_init_kernel, dim3(1), dim3(1), 0, s, w.h);
@@ -676,7 +569,7 @@ extern "C" int dp_cluster_table(const double* points, const int32_t* labels, con
   Ws w;
   if (!ws_carve(workspace, workspace_bytes, n_max, &w)) return DP_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const int g = grid_for(n_max), gc = grid_for((int64_t)max_clusters + 1);
+  const int g = grid_for(n_max, GRID_CAP), gc = grid_for((int64_t)max_clusters + 1, GRID_CAP);
   hipLaunchKernelGGL(tkey_kernel, dim3(g), dim3(256), 0, s, labels, n_dev, n_max, w.keys, w.vals);
   const int rc = dp_sort_pairs((uint64_t*)w.keys, w.vals, n_dev, n_max, 0, 33, w.sortws, w.sort_bytes, stream);
   if (rc) return rc;

@@ -4,6 +4,7 @@
 // Everything is fp64 as numpy computes it; no FMA contraction anywhere in this file, so each
 // product and sum is rounded on its own as numpy's ufuncs do.
 #include "dp_common.h"
+#include "dp_points.h"
 
 #pragma clang fp contract(off)
 
@@ -12,7 +13,7 @@ namespace {
 constexpr int MAX_SEG = DP_GROUND_MAX_SEG;       // 1024
 constexpr int MAX_GRID = DP_GROUND_MAX_GRID;     // 32
 constexpr int LDS_SEG = 32;                      // segments whose 256-bin histograms fit one block's LDS (32 KiB)
-typedef unsigned long long u64;
+constexpr int GRID_CAP = 2048;                   // workgroups of a per-point kernel at the most
 
 // Scratch header at the start of the caller's workspace.  `hist` is zero between passes (the scan
 // kernel clears the rows it read); everything else is cleared at the start of each entry point.
@@ -35,25 +36,6 @@ struct Hdr {
 };
 enum { C_NONFINITE = 0, C_FINITE = 1, C_A = 2, C_B = 3, C_C = 4, C_D = 5, C_SLOT = 6 };
 
-// fp64 -> order-preserving u64 (-0.0 folded onto +0.0) and back
-__device__ __forceinline__ u64 okey(double x) {
-  u64 b = (u64)__double_as_longlong(x);
-  if (x == 0.0) b = 0;
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double unkey(u64 k) {
-  const u64 b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-  return __longlong_as_double((long long)b);
-}
-__device__ __forceinline__ bool fin(double v) { return __builtin_fabs(v) < __builtin_inf(); }   // false for NaN, +-inf
-__device__ __forceinline__ bool finite3(double x, double y, double z) { return fin(x) && fin(y) && fin(z); }
-
-__device__ __forceinline__ int live_n(const int32_t* n_dev, int n_max) {
-  int n = n_dev ? *n_dev : n_max;
-  n = n < 0 ? 0 : n;
-  return n < n_max ? n : n_max;
-}
-
 // One atomic per distinct bin of the wave (pixel neighbours mostly share a segment and a digit).
 __device__ __forceinline__ void wave_hist_add(uint32_t* hist, int bin) {
   const int lane = threadIdx.x & 63;
@@ -65,10 +47,6 @@ __device__ __forceinline__ void wave_hist_add(uint32_t* hist, int bin) {
     if (lane == leader) atomicAdd(&hist[lb], (uint32_t)__popcll(m));
     todo &= ~m;
   }
-}
-__device__ __forceinline__ void wave_count(uint32_t* c, bool p) {
-  const u64 m = __ballot(p);
-  if ((threadIdx.x & 63) == 0 && m) atomicAdd(c, (uint32_t)__popcll(m));
 }
 
 __global__ void hdr_init_kernel(Hdr* h) {
@@ -234,16 +212,11 @@ __global__ void select_final_kernel(Hdr* h, int n_seg, SelRule r, int32_t* count
   if (values_out) values_out[s] = v;
 }
 
-int grid_for(int n_max) {
-  long long g = ((long long)n_max + 255) / 256;
-  return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
-}
-
 // The whole selection on stream s: 8 key passes (+ 4 index passes with `by_index`), then the
 // percentile's neighbour + lerp.  Results stay in the header (value / prefix / idxprefix / ksel).
 void run_select(hipStream_t s, Hdr* h, const double* keys, long long stride, const int32_t* seg, const int32_t* n_dev,
                 int n_max, int n_seg, SelRule r, bool by_index, int32_t* counts_out, double* values_out) {
-  const int g = grid_for(n_max), sg = (n_seg + 63) / 64;
+  const int g = grid_for(n_max, GRID_CAP), sg = (n_seg + 63) / 64;
   const bool lds = n_seg <= LDS_SEG;
   for (int p = 0; p < 8; ++p) {
     const int shift = 56 - 8 * p;
@@ -280,7 +253,7 @@ struct Ws {
 };
 int64_t ws_bytes_for(int64_t n_max) {
   const int64_t n = n_max < 0 ? 0 : n_max;
-  return (int64_t)sizeof(Hdr) + ((n * 4 + 255) / 256) * 256 + n * 8 + 256;
+  return (int64_t)sizeof(Hdr) + al256(n * 4) + n * 8 + 256;
 }
 bool ws_carve(void* ws, int64_t bytes, int n_max, Ws* o) {
   if (!ws || bytes < ws_bytes_for(n_max) || ((uintptr_t)ws & 7)) return false;
@@ -288,7 +261,7 @@ bool ws_carve(void* ws, int64_t bytes, int n_max, Ws* o) {
   o->h = (Hdr*)p;
   p += sizeof(Hdr);
   o->seg = (int32_t*)p;
-  p += (((int64_t)n_max * 4 + 255) / 256) * 256;
+  p += al256((int64_t)n_max * 4);
   o->tmp = (double*)p;
   return true;
 }
@@ -298,28 +271,25 @@ bool ws_carve(void* ws, int64_t bytes, int n_max, Ws* o) {
 __global__ void __launch_bounds__(256) minmax_xz_kernel(const double* __restrict__ pts, const int32_t* n_dev, int n_max,
                                                         Hdr* h) {
   const int n = live_n(n_dev, n_max);
-  u64 k0 = ~0ull, k1 = 0, k2 = ~0ull, k3 = 0;
+  u64 mn[2] = {~0ull, ~0ull}, mx[2] = {0, 0};                    // x, z
   uint32_t bad = 0, good = 0;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
     const double x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
     if (!finite3(x, y, z)) { ++bad; continue; }
     ++good;
-    const u64 kx = okey(x), kz = okey(z);
-    k0 = kx < k0 ? kx : k0; k1 = kx > k1 ? kx : k1;
-    k2 = kz < k2 ? kz : k2; k3 = kz > k3 ? kz : k3;
+    const u64 k[2] = {okey(x), okey(z)};
+    #pragma unroll
+    for (int a = 0; a < 2; ++a) { mn[a] = k[a] < mn[a] ? k[a] : mn[a]; mx[a] = k[a] > mx[a] ? k[a] : mx[a]; }
   }
   #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
-    const u64 a0 = __shfl_xor(k0, o), a1 = __shfl_xor(k1, o), a2 = __shfl_xor(k2, o), a3 = __shfl_xor(k3, o);
-    k0 = a0 < k0 ? a0 : k0; k1 = a1 > k1 ? a1 : k1;
-    k2 = a2 < k2 ? a2 : k2; k3 = a3 > k3 ? a3 : k3;
+    wave_minmax(mn, mx, o);
     bad += __shfl_xor(bad, o);
     good += __shfl_xor(good, o);
   }
   if ((threadIdx.x & 63) == 0) {
     if (good) {
-      atomicMin(&h->mm[0], k0); atomicMax(&h->mm[1], k1);
-      atomicMin(&h->mm[2], k2); atomicMax(&h->mm[3], k3);
+      flush_minmax(h->mm, mn, mx);
       atomicAdd(&h->ctr[C_FINITE], good);
     }
     if (bad) atomicAdd(&h->ctr[C_NONFINITE], bad);
@@ -660,7 +630,7 @@ extern "C" int dp_ground_trace(const double* points, const int32_t* n_dev, int32
   Ws w;
   if (!ws_carve(workspace, workspace_bytes, n_max, &w)) return DP_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const int g = grid_for(n_max);
+  const int g = grid_for(n_max, GRID_CAP);
   clear_hdr(s, w.h);
   hipLaunchKernelGGL(minmax_xz_kernel, dim3(g), dim3(256), 0, s, points, n_dev, n_max, w.h);
   hipLaunchKernelGGL(trace_assign_kernel, dim3(g), dim3(256), 0, s, points, n_dev, n_max, grid_size, w.h, w.seg);
@@ -680,7 +650,7 @@ extern "C" int dp_ground_lowest(const double* points, const int32_t* n_dev, int3
   Ws w;
   if (!ws_carve(workspace, workspace_bytes, n_max, &w)) return DP_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const int g = grid_for(n_max);
+  const int g = grid_for(n_max, GRID_CAP);
   clear_hdr(s, w.h);
   hipLaunchKernelGGL(all_assign_kernel, dim3(g), dim3(256), 0, s, points, n_dev, n_max, w.seg);
   const SelRule r = {DP_SEL_KTH, 0.05, 10, 0};
@@ -701,7 +671,7 @@ extern "C" int dp_ground_dist_percentile(const double* points, const int32_t* n_
   Ws w;
   if (!ws_carve(workspace, workspace_bytes, n_max, &w)) return DP_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const int g = grid_for(n_max);
+  const int g = grid_for(n_max, GRID_CAP);
   clear_hdr(s, w.h);
   const Plane pl = {plane[0], plane[1], plane[2], plane[3]};
   hipLaunchKernelGGL(dist_kernel, dim3(g), dim3(256), 0, s, points, n_dev, n_max, pl, w.h, w.seg, w.tmp);
@@ -720,7 +690,7 @@ extern "C" int dp_ground_normalize(const double* points, double* points_out, con
   Ws w;
   if (!ws_carve(workspace, workspace_bytes, n_max, &w)) return DP_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const int g = grid_for(n_max);
+  const int g = grid_for(n_max, GRID_CAP);
   clear_hdr(s, w.h);
   NormArgs a;
   a.pl = {model[0], model[1], model[2], model[3]};
@@ -745,7 +715,7 @@ extern "C" int dp_ground_adjust(const double* points, double* points_out, const 
   Ws w;
   if (!ws_carve(workspace, workspace_bytes, n_max, &w)) return DP_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const int g = grid_for(n_max), cells = grid_size * grid_size;
+  const int g = grid_for(n_max, GRID_CAP), cells = grid_size * grid_size;
   clear_hdr(s, w.h);
   hipLaunchKernelGGL(minmax_xz_kernel, dim3(g), dim3(256), 0, s, points, n_dev, n_max, w.h);
   hipLaunchKernelGGL(adjust_assign_kernel, dim3(g), dim3(256), 0, s, points, n_dev, n_max, grid_size, w.h, w.seg);

@@ -11,6 +11,7 @@
 // that chunk's hull is the cluster's, and its workgroup goes on to the area and the calipers.
 // No kernel waits on another workgroup; the only serial loops are the two chains over one chunk.
 #include "dp_common.h"
+#include "dp_points.h"
 
 #pragma clang fp contract(off)
 
@@ -28,16 +29,6 @@ struct SHdr {
   int32_t nb[2];                                // hull chunks of the round, by parity
 };
 
-__device__ __forceinline__ int live_n(const int32_t* n_dev, int n_max) {
-  int n = n_dev ? *n_dev : n_max;
-  n = n < 0 ? 0 : n;
-  return n < n_max ? n : n_max;
-}
-__device__ __forceinline__ int table_rows(const int32_t* ncl, int max_clusters) {
-  int k = *ncl;
-  k = k < 0 ? 0 : k;
-  return k < max_clusters ? k : max_clusters;
-}
 // A cluster's range of the cluster-ordered index, kept inside [0, n) whatever `offsets` holds.
 __device__ __forceinline__ int off_at(const int32_t* __restrict__ offsets, int c, int n) {
   const int o = offsets[c];
@@ -46,28 +37,6 @@ __device__ __forceinline__ int off_at(const int32_t* __restrict__ offsets, int c
 __device__ __forceinline__ int count_at(const int32_t* __restrict__ offsets, int c, int n) {
   const int m = off_at(offsets, c + 1, n) - off_at(offsets, c, n);
   return m < 0 ? 0 : m;
-}
-
-// exclusive scan over the 256 threads of the workgroup (wsum: 4 shared words)
-__device__ __forceinline__ int block_excl_scan(int v, int* wsum, int* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int inc = v;
-  #pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(inc, o);
-    if (lane >= o) inc += t;
-  }
-  if (lane == 63) wsum[w] = inc;
-  __syncthreads();
-  int pre = 0, tot = 0;
-  for (int k = 0; k < 4; ++k) {
-    const int s = wsum[k];
-    if (k < w) pre += s;
-    tot += s;
-  }
-  __syncthreads();
-  *total = tot;
-  return pre + inc - v;
 }
 
 // sum over the workgroup, the same value in every thread (red: 4 shared doubles)
@@ -518,7 +487,6 @@ __global__ void __launch_bounds__(NT) hrows_kernel(const int32_t* __restrict__ o
   }
 }
 
-int64_t al256(int64_t b) { return (b + 255) / 256 * 256; }
 // hull chunks of one round at the most: every cluster with a chunk has >= 5 members
 int64_t max_chunks(int64_t n, int64_t k) {
   const int64_t by5 = n / 5;
@@ -573,9 +541,7 @@ extern "C" int dp_cluster_shapes(const double* points, const int32_t* n_dev, int
   Ws w;
   if (!ws_carve(workspace, workspace_bytes, n_max, max_clusters, &w)) return DP_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const int64_t big = n_max > max_clusters ? n_max : max_clusters;
-  const int64_t gi = (big + NT - 1) / NT;
-  const int g = (int)(gi < 1 ? 1 : (gi > 4096 ? 4096 : gi));
+  const int g = grid_for(n_max > max_clusters ? n_max : max_clusters, 4096);
   const int gb = (int)max_chunks(n_max, max_clusters), gc = max_clusters < 1 ? 1 : max_clusters;
   hipLaunchKernelGGL(init_kernel, dim3(g), dim3(NT), 0, s, points, order, offsets, n_dev, n_max, n_clusters_dev, max_clusters,
                      w.guv, shapes_out, w.hcnt, w.done);

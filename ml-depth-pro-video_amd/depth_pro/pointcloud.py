@@ -155,28 +155,37 @@ def read_ply(path: str) -> Tuple[np.ndarray, Optional[np.ndarray]]:
     return np.frombuffer(data[end:], dtype="<f8", count=3 * n).reshape(n, 3).copy(), None
 
 
-# ---- ground-plane fit, levelling, grid adjustment (csrc/dp_ground.hip) ---------------------------
+# ---- what every point-cloud stage checks first -----------------------------------------------------
 
-MAX_GRID = _lib.DP_GROUND_MAX_GRID
+def _count_tensor(count, device):
+    """The live count (None, an int or a tensor) as a device int32 tensor of one element, or None."""
+    if count is None:
+        return None
+    if not torch.is_tensor(count):
+        count = torch.tensor([int(count)], dtype=torch.int32, device=device)
+    return count.detach().to(device=device, dtype=torch.int32).reshape(1)
 
 
-def _ground_args(points: torch.Tensor, count):
+def _points_args(points: torch.Tensor, count, what: str):
+    """(lib, contiguous points, N, device count or None, its pointer or None, stream) of a stage; `what`
+    is the stage's error for a host tensor (it names the stage's source file)."""
     if points.device.type != "cuda":
-        raise _lib.DPError("ground normalisation runs on the ROCm device (csrc/dp_ground.hip)")
+        raise _lib.DPError(what)
     if points.dtype != torch.float64 or points.dim() != 2 or points.shape[1] != 3:
         raise ValueError("points must be an (N, 3) float64 tensor")
     pts = points.contiguous()
     n = pts.shape[0]
     if n >= 2 ** 31:
         raise ValueError("at most 2^31 - 1 points")
-    if count is not None:
-        if not torch.is_tensor(count):
-            count = torch.tensor([int(count)], dtype=torch.int32, device=pts.device)
-        count = count.detach().to(device=pts.device, dtype=torch.int32).reshape(1)
-    lib = _lib.load()
-    ws = torch.empty(int(lib.dp_ground_workspace_size(n)), dtype=torch.uint8, device=pts.device)
+    count = _count_tensor(count, pts.device)
     stream = torch.cuda.current_stream(pts.device).cuda_stream
-    return lib, pts, n, count, (None if count is None else count.data_ptr()), ws, stream
+    return _lib.load(), pts, n, count, (None if count is None else count.data_ptr()), stream
+
+
+# ---- ground-plane fit, levelling, grid adjustment (csrc/dp_ground.hip) ---------------------------
+
+MAX_GRID = _lib.DP_GROUND_MAX_GRID
+_GROUND = "ground normalisation runs on the ROCm device (csrc/dp_ground.hip)"
 
 
 def _check_grid(grid_size: int) -> int:
@@ -203,8 +212,7 @@ def segmented_select(keys: torch.Tensor, seg: torch.Tensor, n_seg: int, *, q: Op
         raise ValueError("keys must be (n,) float64 and seg (n,) int32")
     n, dev = keys.shape[0], keys.device
     lib = _lib.load()
-    if count is not None:
-        count = count.detach().to(device=dev, dtype=torch.int32).reshape(1)
+    count = _count_tensor(count, dev)
     counts = torch.empty(n_seg, dtype=torch.int32, device=dev)
     values = torch.empty(n_seg, dtype=torch.float64, device=dev)
     ws = torch.empty(int(lib.dp_ground_workspace_size(n)), dtype=torch.uint8, device=dev)
@@ -219,7 +227,8 @@ def ground_trace(points: torch.Tensor, count=None, grid_size: int = 20):
     """The fit's ground trace on the device (`dp_ground_trace`), then read back (one synchronisation):
     (trace (g, 4) = mean x, y, z + bin count, valid (g,) bool, info = [finite, non-finite, z_min, z_max])."""
     g = _check_grid(grid_size)
-    lib, pts, n, count, cptr, ws, stream = _ground_args(points, count)
+    lib, pts, n, count, cptr, stream = _points_args(points, count, _GROUND)
+    ws = torch.empty(int(lib.dp_ground_workspace_size(n)), dtype=torch.uint8, device=pts.device)
     blob = torch.empty(g * 4 + 4 + (g + 1) // 2, dtype=torch.float64, device=pts.device)   # trace | info | valid (int32)
     base = blob.data_ptr()
     check(lib.dp_ground_trace(pts.data_ptr(), cptr, n, g, base, base + (g * 4 + 4) * 8, base + g * 32,
@@ -231,7 +240,8 @@ def ground_trace(points: torch.Tensor, count=None, grid_size: int = 20):
 
 def _lowest_points(points: torch.Tensor, count=None) -> np.ndarray:
     """The fit's fallback trace (:702-707): the max(10, int(0.05 n)) lowest-y points, in index order."""
-    lib, pts, n, count, cptr, ws, stream = _ground_args(points, count)
+    lib, pts, n, count, cptr, stream = _points_args(points, count, _GROUND)
+    ws = torch.empty(int(lib.dp_ground_workspace_size(n)), dtype=torch.uint8, device=pts.device)
     cap = min(n, max(10, int(0.05 * n)))
     out = torch.empty(cap, 3, dtype=torch.float64, device=pts.device)
     idx = torch.empty(cap, dtype=torch.int32, device=pts.device)
@@ -246,7 +256,8 @@ def _lowest_points(points: torch.Tensor, count=None) -> np.ndarray:
 def distance_percentile(points: torch.Tensor, normal, d: float, q: float, count=None) -> torch.Tensor:
     """Device tensor [np.percentile(points . normal + d, q), points below the plane, finite points,
     non-finite points] (`dp_ground_dist_percentile`); asynchronous."""
-    lib, pts, n, count, cptr, ws, stream = _ground_args(points, count)
+    lib, pts, n, count, cptr, stream = _points_args(points, count, _GROUND)
+    ws = torch.empty(int(lib.dp_ground_workspace_size(n)), dtype=torch.uint8, device=pts.device)
     out = torch.empty(4, dtype=torch.float64, device=pts.device)
     plane = (ctypes.c_double * 4)(float(normal[0]), float(normal[1]), float(normal[2]), float(d))
     check(lib.dp_ground_dist_percentile(pts.data_ptr(), cptr, n, plane, float(q), out.data_ptr(), ws.data_ptr(),
@@ -346,7 +357,8 @@ def normalize_to_ground(points: torch.Tensor, ground_model: dict, count=None) ->
     """`normalize_point_cloud_to_ground` (:880-981) on the device: (levelled (N, 3) float64 tensor,
     stats (8,) float64 device tensor in `NORMALIZE_STATS` order).  Asynchronous; rows past `count`
     are left uninitialised; points with a non-finite coordinate are copied unchanged and counted."""
-    lib, pts, n, count, cptr, ws, stream = _ground_args(points, count)
+    lib, pts, n, count, cptr, stream = _points_args(points, count, _GROUND)
+    ws = torch.empty(int(lib.dp_ground_workspace_size(n)), dtype=torch.uint8, device=pts.device)
     out = torch.empty_like(pts)
     stats = torch.empty(8, dtype=torch.float64, device=pts.device)
     m = ground_rotation(ground_model)
@@ -363,7 +375,8 @@ def ground_adjust(points: torch.Tensor, grid_size: int = 20, percentile: float =
     g = _check_grid(grid_size)
     if not 0 <= float(percentile) <= 100:
         raise ValueError("percentile must be in [0, 100]")
-    lib, pts, n, count, cptr, ws, stream = _ground_args(points, count)
+    lib, pts, n, count, cptr, stream = _points_args(points, count, _GROUND)
+    ws = torch.empty(int(lib.dp_ground_workspace_size(n)), dtype=torch.uint8, device=pts.device)
     out = torch.empty_like(pts)
     stats = torch.empty(8, dtype=torch.float64, device=pts.device)
     check(lib.dp_ground_adjust(pts.data_ptr(), out.data_ptr(), cptr, n, g, float(percentile), stats.data_ptr(),
@@ -378,23 +391,7 @@ SHADOW_STATS = ("finite", "non_finite", "columns_occupied", "columns_tested", "c
                 "cell_size", "error")
 
 
-def _clean_args(points: torch.Tensor, count):
-    if points.device.type != "cuda":
-        raise _lib.DPError("point-cloud cleaning runs on the ROCm device (csrc/dp_clean.hip)")
-    if points.dtype != torch.float64 or points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError("points must be an (N, 3) float64 tensor")
-    pts = points.contiguous()
-    n = pts.shape[0]
-    if n >= 2 ** 31:
-        raise ValueError("at most 2^31 - 1 points")
-    if count is not None:
-        if not torch.is_tensor(count):
-            count = torch.tensor([int(count)], dtype=torch.int32, device=pts.device)
-        count = count.detach().to(device=pts.device, dtype=torch.int32).reshape(1)
-    lib = _lib.load()
-    ws = torch.empty(int(lib.dp_clean_workspace_size(n)), dtype=torch.uint8, device=pts.device)
-    stream = torch.cuda.current_stream(pts.device).cuda_stream
-    return lib, pts, n, count, (None if count is None else count.data_ptr()), ws, stream
+_CLEAN = "point-cloud cleaning runs on the ROCm device (csrc/dp_clean.hip)"
 
 
 def sort_pairs(keys: torch.Tensor, values: torch.Tensor, count=None, bit_lo: int = 0, bit_hi: int = 64
@@ -414,10 +411,7 @@ def sort_pairs(keys: torch.Tensor, values: torch.Tensor, count=None, bit_lo: int
     n, dev = k.shape[0], k.device
     if n >= 2 ** 31:
         raise ValueError("at most 2^31 - 1 pairs")
-    if count is not None:
-        if not torch.is_tensor(count):
-            count = torch.tensor([int(count)], dtype=torch.int32, device=dev)
-        count = count.detach().to(device=dev, dtype=torch.int32).reshape(1)
+    count = _count_tensor(count, dev)
     lib = _lib.load()
     ws = torch.empty(int(lib.dp_clean_workspace_size(n)), dtype=torch.uint8, device=dev)
     check(lib.dp_sort_pairs(k.data_ptr(), v.data_ptr(), None if count is None else count.data_ptr(), n, int(bit_lo),
@@ -434,7 +428,8 @@ def stray_mask(points: torch.Tensor, count=None, nb_points: int = 20, radius: fl
         raise ValueError(f"nb_points must be >= 1 (got {nb_points})")
     if not (np.isfinite(radius) and float(radius) > 0):
         raise ValueError(f"radius must be finite and > 0 (got {radius})")
-    lib, pts, n, count, cptr, ws, stream = _clean_args(points, count)
+    lib, pts, n, count, cptr, stream = _points_args(points, count, _CLEAN)
+    ws = torch.empty(int(lib.dp_clean_workspace_size(n)), dtype=torch.uint8, device=pts.device)
     keep = torch.empty(n, dtype=torch.uint8, device=pts.device)
     stats = torch.empty(8, dtype=torch.float64, device=pts.device)
     check(lib.dp_clean_stray(pts.data_ptr(), cptr, n, float(radius), int(nb_points), keep.data_ptr(), stats.data_ptr(),
@@ -448,7 +443,8 @@ def shadow_mask(points: torch.Tensor, count=None, shadow_height_threshold: float
     device, asynchronous."""
     if int(min_points_per_column) < 1:
         raise ValueError("min_points_per_column must be >= 1")
-    lib, pts, n, count, cptr, ws, stream = _clean_args(points, count)
+    lib, pts, n, count, cptr, stream = _points_args(points, count, _CLEAN)
+    ws = torch.empty(int(lib.dp_clean_workspace_size(n)), dtype=torch.uint8, device=pts.device)
     keep = torch.empty(n, dtype=torch.uint8, device=pts.device)
     stats = torch.empty(8, dtype=torch.float64, device=pts.device)
     check(lib.dp_clean_shadows(pts.data_ptr(), cptr, n, float(shadow_height_threshold), float(max_shadow_angle),
@@ -460,7 +456,8 @@ def shadow_mask(points: torch.Tensor, count=None, shadow_height_threshold: float
 def compact_points(points: torch.Tensor, colors: Optional[torch.Tensor], keep: torch.Tensor, count=None):
     """`dp_compact_points`: (points buffer (N, 3), colours buffer or None, device int32 count); the
     first `count` rows are the kept rows in their original order, the rest is uninitialised."""
-    lib, pts, n, count, cptr, ws, stream = _clean_args(points, count)
+    lib, pts, n, count, cptr, stream = _points_args(points, count, _CLEAN)
+    ws = torch.empty(int(lib.dp_clean_workspace_size(n)), dtype=torch.uint8, device=pts.device)
     keep = keep.contiguous()
     if keep.dtype not in (torch.uint8, torch.bool) or keep.shape != (n,):
         raise ValueError("keep must be an (N,) uint8 / bool tensor")
@@ -524,21 +521,7 @@ CLUSTER_COLUMNS = ("count", "min_core_row", "x_min", "x_max", "z_min", "z_max", 
                    "sum_z", "reserved")
 
 
-def _cluster_args(points: torch.Tensor, count):
-    if points.device.type != "cuda":
-        raise _lib.DPError("point-cloud clustering runs on the ROCm device (csrc/dp_cluster.hip)")
-    if points.dtype != torch.float64 or points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError("points must be an (N, 3) float64 tensor")
-    pts = points.contiguous()
-    n = pts.shape[0]
-    if n >= 2 ** 31:
-        raise ValueError("at most 2^31 - 1 points")
-    if count is not None:
-        if not torch.is_tensor(count):
-            count = torch.tensor([int(count)], dtype=torch.int32, device=pts.device)
-        count = count.detach().to(device=pts.device, dtype=torch.int32).reshape(1)
-    stream = torch.cuda.current_stream(pts.device).cuda_stream
-    return _lib.load(), pts, n, count, (None if count is None else count.data_ptr()), stream
+_CLUSTER = "point-cloud clustering runs on the ROCm device (csrc/dp_cluster.hip)"
 
 
 def _check_cluster(eps, min_samples, max_points) -> None:
@@ -561,7 +544,7 @@ def dbscan_labels(points: torch.Tensor, count=None, eps: float = 0.2, min_sample
     The returned labels keep the call's workspace alive (it holds the clusters' smallest core rows,
     which `cluster_table` reports)."""
     _check_cluster(eps, min_samples, max_points)
-    lib, pts, n, count, cptr, stream = _cluster_args(points, count)
+    lib, pts, n, count, cptr, stream = _points_args(points, count, _CLUSTER)
     thr = float("nan") if height_threshold is None else float(height_threshold)
     ws = torch.empty(int(lib.dp_cluster_workspace_size(n)), dtype=torch.uint8, device=pts.device)
     labels = torch.empty(n, dtype=torch.int32, device=pts.device)
@@ -583,7 +566,7 @@ def cluster_table(points: torch.Tensor, labels: torch.Tensor, n_clusters: torch.
     come straight from `dbscan_labels` (for any other labels tensor it is -1)."""
     if int(max_clusters) < 0:
         raise ValueError(f"max_clusters must be >= 0 (got {max_clusters})")
-    lib, pts, n, count, cptr, stream = _cluster_args(points, count)
+    lib, pts, n, count, cptr, stream = _points_args(points, count, _CLUSTER)
     if labels.device != pts.device or not torch.is_tensor(n_clusters) or n_clusters.device != pts.device:
         raise _lib.DPError("labels and n_clusters must be on the points' device")
     if labels.dtype != torch.int32 or tuple(labels.shape) != (n,) or not labels.is_contiguous():
@@ -656,7 +639,7 @@ def fit_shapes(points: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor,
         raise ValueError(f"max_clusters must be >= 0 (got {max_clusters})")
     if np.isnan(float(circularity_threshold)):
         raise ValueError("circularity_threshold must not be NaN")
-    lib, pts, n, count, cptr, stream = _cluster_args(points, count)
+    lib, pts, n, count, cptr, stream = _points_args(points, count, _CLUSTER)
     for t in (order, offsets, n_clusters):
         if not torch.is_tensor(t) or t.device != pts.device:
             raise _lib.DPError("order, offsets and n_clusters must be on the points' device")

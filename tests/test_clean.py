@@ -428,6 +428,39 @@ def test_compaction(kind, cuda):
     assert o2.cpu().numpy()[:int(n2.item())].tobytes() == pts[mask].tobytes()
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,kind", [(2047, "random"), (2048, "random"), (2049, "random"), (524288, "random"),
+                                    (524289, "random"), (2049, "none"), (2049, "all")])
+def test_flag_scan_across_tile_edges(n, kind, cuda):
+    """The byte-flag scan the compaction and the clustering share (csrc/dp_points.h), one row either side of a
+    2048-row tile, and at 256 tiles and 256 tiles + 1 row: from there on a thread of the block-offsets kernel
+    walks more than one tile count.  Compaction: kept rows and the device count, exactly.  Clustering (random
+    flags only): the stride sample ranks every eligible row with the same scan; max_points is a third of the
+    eligible rows (1000 at the most, to keep the numpy side quick), against tests/cluster_numpy.py."""
+    import torch
+
+    import cluster_numpy as N
+    from depth_pro import pointcloud as PC
+
+    rng = np.random.default_rng(41)
+    pts = rng.random((n, 3))
+    keep = {"random": rng.random(n) < 0.5, "none": np.zeros(n, bool), "all": np.ones(n, bool)}[kind]
+    P = torch.from_numpy(pts).to(cuda)
+    out, _, n_out = PC.compact_points(P, None, torch.from_numpy(keep).to(cuda))
+    m = int(n_out.item())
+    assert m == keep.sum()
+    assert np.array_equal(out[:m].cpu().numpy(), pts[np.flatnonzero(keep)])
+    if kind != "random":
+        return
+    pts[:, 1] = np.where(keep, 2.0, 0.0)                         # the same flags as eligibility: y >= 1.3
+    mp = min(int(keep.sum()) // 3, 1000)
+    labels, ncl, stats = PC.dbscan_labels(torch.from_numpy(pts).to(cuda), None, 0.05, 4, 1.3, mp)
+    want, _, wstats = N.dbscan(pts, 0.05, 4, 1.3, mp)
+    assert wstats[2] == mp and (want == -2).sum() == n - mp
+    assert np.array_equal(labels.cpu().numpy(), want)
+    assert np.array_equal(stats.cpu().numpy(), wstats) and int(ncl.item()) == int(wstats[6])
+
+
 # ---- GPU: the whole stage and the frame loop ----------------------------------------------------------------------
 
 @pytest.mark.gpu

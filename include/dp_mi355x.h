@@ -41,7 +41,7 @@ enum { DP_A_DENSE = 0, DP_A_CONV = 1 };
 enum { DP_STORE_ROWS = 0, DP_STORE_DECONV2X2 = 1, DP_STORE_HEAD_PS = 2 };
 
 /* ABI version of this header; the Python loader refuses a mismatching .so. */
-#define DP_ABI_VERSION 18
+#define DP_ABI_VERSION 19
 int dp_abi_version(void);
 
 /*
@@ -861,6 +861,90 @@ int dp_cluster_shapes(const double* points, const int32_t* n_dev, int32_t n_max,
                       const int32_t* offsets, const int32_t* n_clusters_dev, int32_t max_clusters,
                       double circularity_threshold, double* shapes_out, int32_t* hull_rows_out,
                       int32_t* hull_offsets_out, void* workspace, int64_t workspace_bytes, dp_stream_t stream);
+
+/*
+ * ---- Oriented mesh points (ABI 19, csrc/dp_normals.hip) --------------------------------------------
+ * The per-point start of the reference's fourth pipeline step, create_mesh_from_pointcloud
+ * (pointcloud_to_mesh.py:313-395).  Every meshing method there begins with the same three Open3D calls
+ * on the cleaned cloud: voxel_down_sample(voxel_size), estimate_normals(KDTreeSearchParamHybrid(radius =
+ * 2 * voxel_size, max_nn = 30)) and orient_normals_towards_camera_location([0, 0, 0]).  (Its first
+ * estimate_normals, on the full cloud, is overwritten by the one after down-sampling and is skipped
+ * here.)  Their product, an oriented point set, is what a surface reconstructor takes as input; Poisson
+ * and ball-pivoting reconstruction and the mesh clean-up are out of scope.  The ground, clean and
+ * cluster sections' conventions hold: fp64 points [n_max][3], n_dev a device int32 (NULL: n_max;
+ * clamped to [0, n_max]), n_max = 0 and *n_dev = 0 valid, everything on the caller's stream with no
+ * synchronisation and no host read-back, each fp64 product, sum and difference rounded on its own (no
+ * FMA), argument errors returned as DP_ERR_* before any launch.  Rows at or beyond the live count are
+ * neither read nor written.
+ *   workspace  >= dp_normals_workspace_size(n_max) bytes of device memory, 8-byte aligned, owned by the
+ *              call until the stream has passed it (content need not be initialised).  About 90 bytes
+ *              per point (the sort's workspace included).
+ *   stats_out  fp64 [8], one layout for the three calls: finite rows, non-finite rows, [2] voxels
+ *              (dp_voxel_downsample) or finite rows with fewer than 3 neighbours (the other two),
+ *              rows whose list was truncated to max_nn (dp_knn_search), flipped normals
+ *              (dp_estimate_normals), error flag, 0, 0.  A call leaves the entries of the others 0.
+ * Open3D was not available to check against, so, as for dp_clean_stray, the sentences below are the
+ * specification (restated in tests/normals_numpy.py, which is pinned to scipy's cKDTree and
+ * numpy.linalg.eigh).
+ *
+ * Voxel grid (dp_voxel_downsample).  Per axis origin = (minimum over the finite live rows) -
+ * voxel_size / 2 and index = floor((v - origin) / voxel_size), clamped to [0, 2^21 - 2].  A voxel is
+ * the set of finite rows with one index triple; its key is (ix << 42) | (iy << 21) | iz.
+ *   points_out    fp64 [n_max][3]: voxel v's point = the mean of its members' coordinates (fp64 sums in
+ *                 an unspecified but fixed order, then one division by the member count)
+ *   colors_out    uint8 [n_max][3] (colors != NULL): per channel (2 * sum + m) / (2 * m) in integers,
+ *                 m the member count: the mean rounded half up
+ *   count_out     int32 [n_max]: voxel v's member count
+ *   voxel_of_out  int32 [n_max]: the voxel of every live row, -1 for a non-finite row
+ *   n_out_dev     device int32: the number of voxels; rows at or beyond it of the three arrays above
+ *                 are not written
+ * Voxels come in ascending key order.  Stated difference: Open3D's order is that of a hash map.
+ * Error flag (device side): an axis would need more than 2^21 - 2 voxels ((max - origin) / voxel_size).
+ * Then *n_out_dev = 0 and voxel_of_out is -1 throughout.  voxel_size not finite or <= 0: DP_ERR_SHAPE.
+ * Method: the cell keys go through dp_sort_pairs with the row as payload (stable, so a voxel's run is in
+ * row order); run heads are flagged and scanned (voxel numbers, *n_out_dev), and one wave per voxel sums
+ * its run.
+ *
+ * Hybrid search (dp_knn_search).  Participants are the finite live rows.  Row j is a neighbour of row i
+ * iff d2 = (dx*dx + dy*dy) + dz*dz < radius*radius -- the expression and strictness of dp_clean_stray;
+ * row i is its own neighbour.  Of more than max_nn neighbours the max_nn smallest by (d2, row) are kept.
+ *   nbr_out        int32 [n_max][max_nn]: row i's neighbours in ascending (d2, row) order, then -1
+ *   nbr_count_out  int32 [n_max]: their number, min(neighbours, max_nn); 0 for a non-finite row
+ * max_nn in [1, 64], radius finite and > 0 (else DP_ERR_SHAPE).
+ * Error flag (device side): an axis would need more than 2^21 - 2 cells of edge radius.  Then every
+ * count is 0 (and every list -1): nothing is listed from a wrong neighbourhood.
+ * Method: the stray stage's grid (cells of edge radius * (1 + 2^-20), dp_sort_pairs, coordinates
+ * gathered into cell order, each of the 9 (x, y) cell rows around a point one key range found by binary
+ * search).  One wave per query: the lanes stride a range's candidates 64 at a time; a batch holding a
+ * candidate below the current max_nn-th smallest is sorted across the lanes (bitonic network on
+ * shuffles) and merged into the running best, kept one entry per lane in ascending order.  No scratch,
+ * no per-thread arrays.
+ *
+ * Normals (dp_estimate_normals), from the lists of a dp_knn_search call (same points, same max_nn).
+ * A finite row with m = nbr_count < 3 listed neighbours gets (0, 0, 1).  Otherwise, over the listed
+ * neighbours in list order: mean = (sum p) / m, then C = (sum (p - mean)(p - mean)^T) / m, two passes,
+ * fp64; the normal is the unit eigenvector of C's smallest eigenvalue (cyclic Jacobi on the 3 x 3 until
+ * the off-diagonal sum no longer changes the diagonal sum, then the column of the smallest diagonal
+ * entry divided by its length).  A zero or non-finite vector becomes (0, 0, 1).  Stated difference:
+ * Open3D accumulates the uncentred moments in one pass and uses a closed-form solver; the eigenvector
+ * is the same up to rounding wherever the two smallest eigenvalues are apart, its sign is arbitrary in
+ * both.  With orient != 0 the normal (the (0, 0, 1) default included, as in Open3D) is negated when
+ * (nx * (cx - px) + ny * (cy - py)) + nz * (cz - pz) < 0 with c = camera (HOST pointer, fp64 [3],
+ * finite).  A non-finite row gets (0, 0, 0).  An entry of a list outside [0, live count) ends the list.
+ *   normals_out  fp64 [n_max][3]
+ * One thread per row; both passes gather the neighbours' coordinates, everything else is in registers.
+ */
+int64_t dp_normals_workspace_size(int64_t n_max);
+int dp_voxel_downsample(const double* points, const uint8_t* colors, const int32_t* n_dev, int32_t n_max,
+                        double voxel_size, double* points_out, uint8_t* colors_out, int32_t* count_out,
+                        int32_t* voxel_of_out, int32_t* n_out_dev, double* stats_out, void* workspace,
+                        int64_t workspace_bytes, dp_stream_t stream);
+int dp_knn_search(const double* points, const int32_t* n_dev, int32_t n_max, double radius, int32_t max_nn,
+                  int32_t* nbr_out, int32_t* nbr_count_out, double* stats_out, void* workspace,
+                  int64_t workspace_bytes, dp_stream_t stream);
+int dp_estimate_normals(const double* points, const int32_t* n_dev, int32_t n_max, const int32_t* nbr,
+                        const int32_t* nbr_count, int32_t max_nn, const double* camera, int32_t orient,
+                        double* normals_out, double* stats_out, dp_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -23,6 +23,11 @@ and the host-side `cluster_summary` -- csrc/dp_cluster.hip, no sklearn, no host 
 `fit_shapes` / `cluster_shapes` fit each cluster's convex hull, minimum-area rectangle and circle and take
 the reference's circle-or-rectangle decision (csrc/dp_shapes.hip, no scipy, no OpenCV); `shape_summary` and
 `export_shape_text` are their host-side writers.
+
+Oriented mesh points (the start of the reference's meshing step, `pointcloud_to_mesh.py:313-395`):
+`voxel_downsample`, `knn_search`, `estimate_normals` and `oriented_points` (all three with the reference's
+values) -- csrc/dp_normals.hip, no Open3D, no host read-back; `write_ply_normals` / `read_ply_normals` are the
+PLY writer and reader for a cloud with normals.
 """
 
 from __future__ import annotations
@@ -736,6 +741,202 @@ def export_shape_text(summary: dict, path: str) -> None:
         for i, c in enumerate(circles):
             f.write(f"{len(rects) + i + 1}, {c['center'][0]:.3f}, {c['center'][1]:.3f}, {c['radius']:.3f}, "
                     f"{np.pi * c['radius'] ** 2:.3f}\n")
+
+
+# ---- oriented mesh points: voxel grid, hybrid search, normals (csrc/dp_normals.hip) -----------------
+
+VOXEL_STATS = ("finite", "non_finite", "voxels", "reserved0", "reserved1", "error", "reserved2", "reserved3")
+KNN_STATS = ("finite", "non_finite", "few_neighbors", "truncated", "reserved0", "error", "reserved1", "reserved2")
+NORMAL_STATS = ("finite", "non_finite", "few_neighbors", "truncated", "flipped", "error", "reserved0", "reserved1")
+MAX_NN = 64
+
+_NORMALS = "oriented mesh points run on the ROCm device (csrc/dp_normals.hip)"
+
+
+def _check_search(radius, max_nn) -> None:
+    if not (np.isfinite(float(radius)) and float(radius) > 0):
+        raise ValueError(f"radius must be finite and > 0 (got {radius})")
+    if not 1 <= int(max_nn) <= MAX_NN:
+        raise ValueError(f"max_nn must be in [1, {MAX_NN}] (got {max_nn})")
+
+
+def voxel_downsample(points: torch.Tensor, colors: Optional[torch.Tensor] = None, count=None, voxel_size: float = 0.05):
+    """Open3D's `voxel_down_sample(voxel_size)` on the device (`dp_voxel_downsample`): (points buffer (N, 3),
+    colours buffer or None, members per voxel (N,) int32, voxel of every input row (N,) int32 -- -1 for a
+    non-finite row --, device int32 voxel count, stats (8,) float64 in `VOXEL_STATS` order).  The first
+    `count` rows of the first three are the voxels, in ascending order of their packed grid index (Open3D's
+    order is a hash map's); a voxel's point is the mean of its members, its colour the mean rounded half up.
+    Asynchronous, no read-back.  A cloud spanning more than 2^21 - 2 voxels on an axis raises
+    stats["error"] and gives no voxels."""
+    if not (np.isfinite(float(voxel_size)) and float(voxel_size) > 0):
+        raise ValueError(f"voxel_size must be finite and > 0 (got {voxel_size})")
+    lib, pts, n, count, cptr, stream = _points_args(points, count, _NORMALS)
+    cols = None
+    if colors is not None:
+        cols = colors.contiguous()
+        if cols.dtype != torch.uint8 or tuple(cols.shape) != (n, 3):
+            raise ValueError("colors must be an (N, 3) uint8 tensor")
+    dev = pts.device
+    ws = torch.empty(int(lib.dp_normals_workspace_size(n)), dtype=torch.uint8, device=dev)
+    out = torch.empty_like(pts)
+    cout = None if cols is None else torch.empty_like(cols)
+    members = torch.empty(n, dtype=torch.int32, device=dev)
+    voxel_of = torch.empty(n, dtype=torch.int32, device=dev)
+    n_out = torch.empty(1, dtype=torch.int32, device=dev)
+    stats = torch.empty(8, dtype=torch.float64, device=dev)
+    check(lib.dp_voxel_downsample(pts.data_ptr(), None if cols is None else cols.data_ptr(), cptr, n, float(voxel_size),
+                                  out.data_ptr(), None if cout is None else cout.data_ptr(), members.data_ptr(),
+                                  voxel_of.data_ptr(), n_out.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(), stream),
+          "dp_voxel_downsample")
+    return out, cout, members, voxel_of, n_out, stats
+
+
+def knn_search(points: torch.Tensor, count=None, radius: float = 0.1, max_nn: int = 30):
+    """Open3D's `KDTreeSearchParamHybrid(radius, max_nn)` for every row at once (`dp_knn_search`): (neighbours
+    (N, max_nn) int32 -- row numbers in ascending (squared distance, row) order, the row itself first, padded
+    with -1 --, their number (N,) int32, stats (8,) float64 in `KNN_STATS` order).  A neighbour lies at squared
+    distance (dx*dx + dy*dy) + dz*dz < radius*radius, as in `remove_stray_points`; non-finite rows have none.
+    Asynchronous, no read-back; rows past `count` are not written.  A cloud spanning more than 2^21 - 2 cells
+    of edge `radius` on an axis raises stats["error"] and every count is 0."""
+    _check_search(radius, max_nn)
+    lib, pts, n, count, cptr, stream = _points_args(points, count, _NORMALS)
+    dev = pts.device
+    ws = torch.empty(int(lib.dp_normals_workspace_size(n)), dtype=torch.uint8, device=dev)
+    nbr = torch.empty(n, int(max_nn), dtype=torch.int32, device=dev)
+    cnt = torch.empty(n, dtype=torch.int32, device=dev)
+    stats = torch.empty(8, dtype=torch.float64, device=dev)
+    check(lib.dp_knn_search(pts.data_ptr(), cptr, n, float(radius), int(max_nn), nbr.data_ptr(), cnt.data_ptr(),
+                            stats.data_ptr(), ws.data_ptr(), ws.numel(), stream), "dp_knn_search")
+    return nbr, cnt, stats
+
+
+def normals_from_neighbors(points: torch.Tensor, nbr: torch.Tensor, nbr_count: torch.Tensor, count=None,
+                           camera_location=(0, 0, 0), orient: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`dp_estimate_normals` on the lists of a `knn_search` over the same points: (normals (N, 3) float64, stats
+    (8,) float64 -- finite, non-finite, rows with fewer than 3 neighbours, 0, flipped, 0, 0, 0)."""
+    lib, pts, n, count, cptr, stream = _points_args(points, count, _NORMALS)
+    if nbr.device != pts.device or nbr_count.device != pts.device:
+        raise _lib.DPError("nbr and nbr_count must be on the points' device")
+    if nbr.dtype != torch.int32 or nbr.dim() != 2 or nbr.shape[0] != n or not nbr.is_contiguous() or \
+            not 1 <= nbr.shape[1] <= MAX_NN:
+        raise ValueError(f"nbr must be a contiguous (N, max_nn <= {MAX_NN}) int32 tensor")
+    if nbr_count.dtype != torch.int32 or tuple(nbr_count.shape) != (n,) or not nbr_count.is_contiguous():
+        raise ValueError("nbr_count must be a contiguous (N,) int32 tensor")
+    cam = [float(v) for v in camera_location]
+    if len(cam) != 3 or not all(np.isfinite(cam)):
+        raise ValueError("camera_location must be three finite numbers")
+    normals = torch.empty_like(pts)
+    stats = torch.empty(8, dtype=torch.float64, device=pts.device)
+    check(lib.dp_estimate_normals(pts.data_ptr(), cptr, n, nbr.data_ptr(), nbr_count.data_ptr(), int(nbr.shape[1]),
+                                  (ctypes.c_double * 3)(*cam), int(bool(orient)), normals.data_ptr(), stats.data_ptr(),
+                                  stream), "dp_estimate_normals")
+    return normals, stats
+
+
+def estimate_normals(points: torch.Tensor, count=None, radius: float = 0.1, max_nn: int = 30, camera_location=(0, 0, 0),
+                     orient: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Open3D's `estimate_normals(KDTreeSearchParamHybrid(radius, max_nn))` and, with `orient`,
+    `orient_normals_towards_camera_location(camera_location)` on the device: `knn_search`, then per row the unit
+    eigenvector of the smallest eigenvalue of its neighbours' centred covariance (two passes, fp64), negated where
+    it points away from the camera.  Fewer than 3 neighbours give (0, 0, 1) (oriented like any other), a
+    non-finite row (0, 0, 0).  Returns (normals (N, 3) float64, stats (8,) float64 in `NORMAL_STATS` order: the
+    search's `truncated` and `error` beside the normals' own counts).  Asynchronous, no read-back.
+    Stated difference: Open3D uses the one-pass uncentred moments and a closed-form solver."""
+    nbr, cnt, kst = knn_search(points, count, radius, max_nn)
+    normals, stats = normals_from_neighbors(points, nbr, cnt, count, camera_location, orient)
+    stats[3] = kst[3]
+    stats[5] = kst[5]
+    return normals, stats
+
+
+def oriented_points(points: torch.Tensor, colors: Optional[torch.Tensor] = None, count=None, voxel_size: float = 0.05,
+                    max_nn: int = 30, camera_location=(0, 0, 0)):
+    """What every meshing method of the reference's `create_mesh_from_pointcloud` (pointcloud_to_mesh.py:313-395)
+    starts from: `voxel_downsample(voxel_size)`, then `estimate_normals` with radius = 2 * voxel_size and `max_nn`
+    (the reference's values), oriented towards `camera_location`.  Returns (points buffer, colours buffer or
+    None, device int32 count, normals buffer, voxel stats, normal stats); the first `count` rows are the
+    oriented point set.  (The reference's first `estimate_normals`, on the full cloud, is overwritten by this
+    one and is not computed.)  On the device, nothing synchronised."""
+    out, cout, _, _, n_out, vst = voxel_downsample(points, colors, count, voxel_size)
+    normals, nst = estimate_normals(out, n_out, 2.0 * float(voxel_size), max_nn, camera_location, True)
+    return out, cout, n_out, normals, vst, nst
+
+
+PLY_NORMALS_RECORD = 51   # bytes per vertex: double x, y, z, nx, ny, nz + uchar red, green, blue
+
+
+def _ply_normals_header(n: int, colored: bool) -> bytes:
+    props = [f"property double {k}" for k in ("x", "y", "z", "nx", "ny", "nz")]
+    if colored:
+        props += ["property uchar red", "property uchar green", "property uchar blue"]
+    return ("\n".join(["ply", "format binary_little_endian 1.0", f"element vertex {n}", *props, "end_header"])
+            + "\n").encode("ascii")
+
+
+def write_ply_normals(path: str, points: np.ndarray, normals: np.ndarray, colors: Optional[np.ndarray] = None) -> str:
+    """Binary little-endian PLY: double x, y, z, nx, ny, nz (+ uchar red, green, blue) -- the vertex layout
+    Open3D writes for a cloud with normals."""
+    pts = np.asarray(points, dtype="<f8").reshape(-1, 3)
+    nrm = np.asarray(normals, dtype="<f8").reshape(-1, 3)
+    n = pts.shape[0]
+    if nrm.shape[0] != n:
+        raise ValueError("points and normals differ in length")
+    if colors is not None:
+        col = np.asarray(colors, dtype=np.uint8).reshape(-1, 3)
+        if col.shape[0] != n:
+            raise ValueError("points and colors differ in length")
+        body = np.empty(n, dtype=[("p", "<f8", 3), ("n", "<f8", 3), ("c", "u1", 3)])
+        body["c"] = col
+    else:
+        body = np.empty(n, dtype=[("p", "<f8", 3), ("n", "<f8", 3)])
+    body["p"], body["n"] = pts, nrm
+    if not path.endswith(".ply"):
+        path = path + ".ply"
+    with open(path, "wb") as f:
+        f.write(_ply_normals_header(n, colors is not None))
+        f.write(memoryview(body.view(np.uint8)))
+    return path
+
+
+def ply_normals_records_async(xyz: torch.Tensor, normals: torch.Tensor, cols: Optional[torch.Tensor]) -> torch.Tensor:
+    """The vertex records `write_ply_normals` writes, interleaved on the device ((N, 51) uint8, or (N, 48) without
+    colours), queued on the current stream, no sync -- `ply_records_async` for a cloud with normals."""
+    n = xyz.shape[0]
+    width = PLY_NORMALS_RECORD if cols is not None else PLY_NORMALS_RECORD - 3
+    rec = torch.empty(n, width, dtype=torch.uint8, device=xyz.device)
+    rec[:, :24].copy_(xyz.contiguous().view(torch.uint8).view(n, 24))
+    rec[:, 24:48].copy_(normals.contiguous().view(torch.uint8).view(n, 24))
+    if cols is not None:
+        rec[:, 48:].copy_(cols.view(n, 3))
+    return rec
+
+
+def write_ply_normals_records(path: str, records: np.ndarray) -> str:
+    """`write_ply_normals` for vertex records already in file layout (`ply_normals_records_async`)."""
+    rec = np.ascontiguousarray(records, dtype=np.uint8)
+    if rec.ndim != 2 or rec.shape[1] not in (PLY_NORMALS_RECORD, PLY_NORMALS_RECORD - 3):
+        raise ValueError(f"records must be (n, {PLY_NORMALS_RECORD}) or (n, {PLY_NORMALS_RECORD - 3}) uint8")
+    if not path.endswith(".ply"):
+        path = path + ".ply"
+    with open(path, "wb") as f:
+        f.write(_ply_normals_header(rec.shape[0], rec.shape[1] == PLY_NORMALS_RECORD))
+        f.write(memoryview(rec.reshape(-1)))            # flat first: a frame may leave no points
+    return path
+
+
+def read_ply_normals(path: str) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
+    """Reader for the files `write_ply_normals` produces: (points, normals, colours or None).  (`read_ply` keeps
+    reading the files without normals; it is not extended, so nothing changes for them.)"""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    lines = data[:end].decode("ascii").splitlines()
+    n = int(next(l for l in lines if l.startswith("element vertex")).split()[-1])
+    if not any(l == "property double nx" for l in lines):
+        raise ValueError(f"{path} has no normals")
+    dt = [("p", "<f8", 3), ("n", "<f8", 3)] + ([("c", "u1", 3)] if any("red" in l for l in lines) else [])
+    rec = np.frombuffer(data[end:], dtype=dt, count=n)
+    return rec["p"].copy(), rec["n"].copy(), (rec["c"].copy() if len(dt) == 3 else None)
 
 
 GROUND_JSON = "ground.json"

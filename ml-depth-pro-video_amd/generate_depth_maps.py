@@ -250,21 +250,33 @@ def shapes_name(image_path: str) -> str:
     return f"{os.path.splitext(os.path.basename(image_path))[0]}_shapes.json"
 
 
+def oriented_name(image_path: str) -> str:
+    """`{base}_oriented.ply` (--mesh_points); its parameters and statistics go to `{base}_oriented.json` beside it."""
+    return f"{os.path.splitext(os.path.basename(image_path))[0]}_oriented.ply"
+
+
+def oriented_json_name(image_path: str) -> str:
+    return f"{os.path.splitext(os.path.basename(image_path))[0]}_oriented.json"
+
+
 def plan_frames(image_paths, output_dir: str, world: int, rank: int, resume: bool, cleaned: bool = False,
-                clustered: bool = False, shaped: bool = False) -> List[int]:
+                clustered: bool = False, shaped: bool = False, oriented: bool = False) -> List[int]:
     """Indices of the frames this rank processes: the frames still to do (all of them, or with
     `resume` those whose output file is missing -- decided by rank 0 alone and broadcast before
     any rank writes, so every rank shards the same list), dealt round-robin over the ranks.
     `cleaned` (--clean_pointcloud): a frame also counts as missing without its `{base}_clean.ply`;
     `clustered` (--cluster_pointcloud): and without its `{base}_clusters.json`; `shaped` (--fit_shapes): and
-    without its `{base}_shapes.json`."""
+    without its `{base}_shapes.json`; `oriented` (--mesh_points): and without its `{base}_oriented.ply` or
+    `{base}_oriented.json`."""
     todo = list(range(len(image_paths)))
     if resume:
         if rank == 0:
             done = lambda k: os.path.exists(os.path.join(output_dir, output_name(image_paths[k]))) and (   # noqa: E731
                 not cleaned or os.path.exists(os.path.join(output_dir, cloud_name(image_paths[k], True)))) and (
                 not clustered or os.path.exists(os.path.join(output_dir, clusters_name(image_paths[k])))) and (
-                not shaped or os.path.exists(os.path.join(output_dir, shapes_name(image_paths[k]))))
+                not shaped or os.path.exists(os.path.join(output_dir, shapes_name(image_paths[k])))) and (
+                not oriented or (os.path.exists(os.path.join(output_dir, oriented_name(image_paths[k]))) and
+                                 os.path.exists(os.path.join(output_dir, oriented_json_name(image_paths[k])))))
             todo = [k for k in todo if not done(k)]
         if world > 1:
             box = [todo]
@@ -279,7 +291,7 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                               ground_percentile=5, rotation_offset=None, clean_pointcloud=False, stray_radius=0.1,
                               stray_neighbors=20, cluster_pointcloud=False, cluster_eps=0.2, cluster_min_samples=5,
                               cluster_height=1.3, cluster_max_points=100000, fit_shapes=False,
-                              circularity_threshold=0.85):
+                              circularity_threshold=0.85, mesh_points=False, voxel_size=0.05, normals_max_nn=30):
     """Directory loop (reference :153-206), pipelined decode -> GPU -> encode, frame-sharded across ranks.
 
     Every rank writes its own frames' files; each frame has exactly one owner.  resume=True skips
@@ -309,6 +321,11 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
     and circle on the same stream right after the cluster table (`PC.fit_shapes`, with the reference's
     circle-or-rectangle decision at circularity_threshold) and writes `{base}_shapes.json`
     (`PC.shape_summary`) and `{base}_shapes.txt` (the reference's `export_shape_data` layout).
+    mesh_points=True (implies clean_pointcloud) turns the cleaned cloud into the oriented point set every meshing
+    method of the reference's pointcloud_to_mesh.py starts from (`PC.oriented_points`: voxel grid of voxel_size,
+    normals over radius 2 * voxel_size and at most normals_max_nn neighbours, oriented towards the origin) on the
+    same stream and writes `{base}_oriented.ply` (double x y z nx ny nz + uchar rgb) and `{base}_oriented.json`
+    (parameters, point count, both statistics); without it the loop writes exactly what it wrote before.
     `model`: an already-built (model, transform) pair (tests); default: `_model`.
     Returns the number of frames this rank wrote.
     """
@@ -316,6 +333,11 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
     clean = None
     cluster = None
     shapes = None
+    mesh = None
+    if mesh_points:
+        check_mesh(voxel_size, normals_max_nn)
+        clean_pointcloud = True
+        mesh = {"voxel_size": float(voxel_size), "max_nn": int(normals_max_nn)}
     if fit_shapes:
         check_circularity(circularity_threshold)
         cluster_pointcloud = True
@@ -343,7 +365,7 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
     if ground is not None:
         ground["world"], ground["rank"] = world, rank
     mine = plan_frames(image_paths, output_dir, world, rank, resume, cleaned=clean is not None,
-                       clustered=cluster is not None, shaped=shapes is not None)
+                       clustered=cluster is not None, shaped=shapes is not None, oriented=mesh is not None)
     print(f"[rank {rank}/{world}] Found {len(image_paths)} images, processing {len(mine)}")
     if model is None:
         model = _model(_device(), half_precision)
@@ -400,7 +422,8 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                     host = _image_async(depth, colored, cmap)
                     gpu_img = True
                     if pointcloud:
-                        pc = _points(depth, pred["focallength_px"], image, ground, image_paths[k], clean, cluster, shapes)
+                        pc = _points(depth, pred["focallength_px"], image, ground, image_paths[k], clean, cluster, shapes,
+                                     mesh)
                     ev = torch.cuda.Event()
                     ev.record()
                 else:
@@ -410,7 +433,9 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                             cloud=os.path.join(output_dir, cloud_name(image_paths[k], clean is not None)),
                             cjson=os.path.join(output_dir, clusters_name(image_paths[k])),
                             cnpy=os.path.join(output_dir, labels_name(image_paths[k])),
-                            sjson=os.path.join(output_dir, shapes_name(image_paths[k]))):
+                            sjson=os.path.join(output_dir, shapes_name(image_paths[k])),
+                            oply=os.path.join(output_dir, oriented_name(image_paths[k])),
+                            ojson=os.path.join(output_dir, oriented_json_name(image_paths[k]))):
                     if ev is not None:
                         ev.synchronize()
                     if status is not None:
@@ -421,6 +446,8 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                             _write_clusters(pc, cluster, cjson, cnpy)
                         if shapes is not None:
                             _write_shapes(pc, cluster, shapes, sjson)
+                        if mesh is not None:
+                            _write_oriented(pc[-1], mesh, oply, ojson)
                     if gpu_img:
                         _write_png(path, _host_image(host))
                         return path
@@ -470,6 +497,13 @@ def check_circularity(threshold) -> None:
         raise ValueError("--circularity_threshold must not be nan")
 
 
+def check_mesh(voxel_size, max_nn) -> None:
+    if not (np.isfinite(float(voxel_size)) and float(voxel_size) > 0):
+        raise ValueError(f"--voxel_size must be finite and > 0 (got {voxel_size})")
+    if not 1 <= int(max_nn) <= PC.MAX_NN:
+        raise ValueError(f"--normals_max_nn must be in [1, {PC.MAX_NN}] (got {max_nn})")
+
+
 MAX_CLUSTERS = 4096     # rows of the per-frame cluster table (a frame with more lists the first 4096)
 
 
@@ -508,7 +542,8 @@ def _ground_plane(ground: dict, xyz, count, image_path):
     return model
 
 
-def _points(depth: torch.Tensor, f_px, image, ground=None, image_path=None, clean=None, cluster=None, shapes=None):
+def _points(depth: torch.Tensor, f_px, image, ground=None, image_path=None, clean=None, cluster=None, shapes=None,
+            mesh=None):
     """Queue the frame's point cloud on the GPU (depth_to_3d, img_to_normalized_pointcloud.py:819-856),
     interleaved into PLY vertex records there, and their copy into a pinned host buffer, on the
     current stream, without a host synchronisation: the full-size record buffer + the point count
@@ -542,6 +577,18 @@ def _points(depth: torch.Tensor, f_px, image, ground=None, image_path=None, clea
         hbuf = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
         hbuf.copy_(t, non_blocking=True)
         out.append(hbuf)
+    if mesh is not None:
+        # the oriented point set of the cleaned cloud (--mesh_points): voxel grid, normals, orientation, and the PLY
+        # records, queued on the same stream.  Only the voxel count and the statistics are copied here; the records
+        # stay on the device (their number is not known on the host yet) and the writer fetches exactly that many.
+        op, oc, on, onrm, vst, nst = PC.oriented_points(xyz, cols, count, mesh["voxel_size"], mesh["max_nn"])
+        small = []
+        for t in (on.reshape(()), vst, nst):
+            hbuf = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+            hbuf.copy_(t, non_blocking=True)
+            small.append(hbuf)
+        out.append({"records": PC.ply_normals_records_async(op, onrm, oc), "count": small[0], "voxel_stats": small[1],
+                    "normal_stats": small[2]})
     return tuple(out)
 
 
@@ -573,6 +620,28 @@ def _write_shapes(pc, cluster: dict, shapes: dict, json_path: str) -> None:
     with open(json_path, "w") as f:
         json.dump(summary, f, indent=1)
     PC.export_shape_text(summary, os.path.splitext(json_path)[0] + ".txt")
+
+
+def _write_oriented(m: dict, mesh: dict, ply_path: str, json_path: str) -> None:
+    """Writer-thread side (after the frame's event, so the records are complete): fetch the first `count` records
+    on a stream of this thread's own, then `{base}_oriented.ply` and `{base}_oriented.json`."""
+    import json
+
+    rec = m["records"]
+    n = max(0, min(int(m["count"]), rec.shape[0]))
+    side = torch.cuda.Stream(rec.device)
+    with torch.cuda.stream(side):
+        host = torch.empty((n, rec.shape[1]), dtype=rec.dtype, pin_memory=True)
+        host.copy_(rec[:n], non_blocking=True)
+    side.synchronize()
+    PC.write_ply_normals_records(ply_path, host.numpy())
+    summary = {"parameters": {"voxel_size": mesh["voxel_size"], "radius": 2.0 * mesh["voxel_size"], "max_nn": mesh["max_nn"],
+                              "camera_location": [0.0, 0.0, 0.0]},
+               "points": n,
+               "voxel_stats": {k: float(v) for k, v in zip(PC.VOXEL_STATS, m["voxel_stats"].numpy())},
+               "normal_stats": {k: float(v) for k, v in zip(PC.NORMAL_STATS, m["normal_stats"].numpy())}}
+    with open(json_path, "w") as f:
+        json.dump(summary, f, indent=1)
 
 
 def main():
@@ -620,10 +689,17 @@ def main():
                              "{frame}_shapes.json and the floor-plan text {frame}_shapes.txt")
     parser.add_argument("--circularity_threshold", type=float, default=0.85,
                         help="Hull area over circle area above which a cluster may be a circle (default 0.85)")
+    parser.add_argument("--mesh_points", action="store_true",
+                        help="Write the oriented point set a mesher starts from (implies --clean_pointcloud): voxel grid, "
+                             "normals, orientation towards the camera; {frame}_oriented.ply and {frame}_oriented.json")
+    parser.add_argument("--voxel_size", type=float, default=0.05,
+                        help="Voxel edge of --mesh_points in metres (default 0.05); normals use radius 2 * voxel_size")
+    parser.add_argument("--normals_max_nn", type=int, default=30,
+                        help=f"Neighbours at the most per normal (1..{PC.MAX_NN}, default 30)")
     parser.add_argument("--resume", action="store_true",
                         help="Skip frames whose {frame}_depth.png (with --clean_pointcloud: and {frame}_clean.ply; with "
-                             "--cluster_pointcloud: and {frame}_clusters.json; with --fit_shapes: and {frame}_shapes.json) already "
-                             "exists in --output_dir")
+                             "--cluster_pointcloud: and {frame}_clusters.json; with --fit_shapes: and {frame}_shapes.json; with "
+                             "--mesh_points: and {frame}_oriented.ply / .json) already exists in --output_dir")
     parser.add_argument("--colormap", type=str, default="turbo",
                         choices=["turbo", "viridis", "plasma", "inferno", "magma", "cividis", "jet"],
                         help="Colormap for depth visualization")
@@ -636,6 +712,8 @@ def main():
         check_stray(args.stray_radius, args.stray_neighbors)
         check_cluster(args.cluster_eps, args.cluster_min_samples, args.cluster_max_points)
         check_circularity(args.circularity_threshold)
+        if args.mesh_points:
+            check_mesh(args.voxel_size, args.normals_max_nn)
     except ValueError as e:
         parser.error(str(e))
     batch_generate_depth_maps(input_dir=args.input_dir, output_dir=args.output_dir, pattern=args.pattern,
@@ -649,7 +727,8 @@ def main():
                               stray_neighbors=args.stray_neighbors, cluster_pointcloud=args.cluster_pointcloud,
                               cluster_eps=args.cluster_eps, cluster_min_samples=args.cluster_min_samples,
                               cluster_height=args.cluster_height, cluster_max_points=args.cluster_max_points,
-                              fit_shapes=args.fit_shapes, circularity_threshold=args.circularity_threshold)
+                              fit_shapes=args.fit_shapes, circularity_threshold=args.circularity_threshold,
+                              mesh_points=args.mesh_points, voxel_size=args.voxel_size, normals_max_nn=args.normals_max_nn)
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()

@@ -44,6 +44,8 @@ def main():
                     help="cluster the cleaned clouds (--cluster_pointcloud of the loop; implies --clean-pointcloud)")
     ap.add_argument("--fit-shapes", action="store_true",
                     help="fit the clusters' shapes (--fit_shapes of the loop; implies --cluster-pointcloud)")
+    ap.add_argument("--mesh-points", action="store_true",
+                    help="write the oriented mesh points (--mesh_points of the loop; implies --clean-pointcloud)")
     ap.add_argument("--raw", action="store_true")
     ap.add_argument("--workers", type=int, default=None,
                     help="decode and encode threads each (default: the loop's own defaults)")
@@ -132,7 +134,7 @@ def main():
     t_setup = time.time() - t
     if args.fit_shapes:
         args.cluster_pointcloud = True
-    if args.cluster_pointcloud:
+    if args.cluster_pointcloud or args.mesh_points:
         args.clean_pointcloud = True
     if args.clean_pointcloud:
         args.normalize_ground = True
@@ -147,6 +149,8 @@ def main():
         kw["cluster_pointcloud"] = True
     if args.fit_shapes:
         kw["fit_shapes"] = True
+    if args.mesh_points:
+        kw["mesh_points"] = True
     if args.workers:
         kw.update(decode_workers=args.workers, encode_workers=args.workers)
     import inspect
@@ -233,7 +237,7 @@ def main():
         "what": "generate_depth_maps.batch_generate_depth_maps end to end, 1 GPU",
         "frames": args.frames, "size": [W, H], "pointcloud": args.pointcloud, "normalize_ground": args.normalize_ground,
         "clean_pointcloud": args.clean_pointcloud, "cluster_pointcloud": args.cluster_pointcloud,
-        "fit_shapes": args.fit_shapes,
+        "fit_shapes": args.fit_shapes, "mesh_points": args.mesh_points,
         "raw": args.raw,
         "ply_records": "host (numpy)" if args.ply_host else "GPU",
         "png_writer": "bytes copies" if args.png_copy else "zero-copy parts",

@@ -180,7 +180,8 @@ int gemm_plan(const dp_gemm_args* a, GemmP& p, int& tile) {
       const bool cv3 = a->a_mode == DP_A_CONV && a->k_h == 3 && a->k_w == 3 && a->stride == 1 && a->pad == 1 &&
                        a->in_h == a->in_w && a->out_h == a->in_h && a->out_w == a->in_w && a->in_w % 16 == 0 &&
                        a->in_c % 64 == 0 && a->head_corr && a->store_mode == DP_STORE_ROWS && a->c_dtype != DP_F32 &&
-                       !a->R1 && !a->R2 && !a->gamma && !a->pos && !a->accumulate && !a->row_group && !(dbg & 4096);
+                       !a->R1 && !a->R2 && !a->gamma && !a->pos && !a->accumulate && !a->row_group && !(dbg & 4096) &&
+                       (long long)a->M * a->in_c < (1LL << 30);   // (the patch DMA's 2-GiB input map; else 512 x 128)
       tile = !cv3 ? DP_TILE_BIG_512x128
              : a->in_w % 48 == 0 ? DP_TILE_CV3_384x128 : DP_TILE_CV3_256x256;
     }

@@ -54,11 +54,13 @@ constexpr int CV_EPI_RES = 0, CV_EPI_BC = 1, CV_EPI_HPS = 2;
 // normal kernel plus per-workgroup clock stamps into g_cv3_stamp (tools/cv3_stamps.py); 16: no
 // barriers in the K loop; 32: the A fragments' ReLU applied by the reading wave; 64: no weight
 // LDS-DMA in the K loop; 128: no patch LDS-DMA in the K loop; 256 (with 8): wave 0's K-loop cycles by
-// kind into stamps 6..9; 512: static priority (waves 4-7 at
+// kind into stamps 6..15, the tap-0 steps apart; 512: static priority (waves 4-7 at
 // priority 1 through the K loop) instead of a raise / drop around every MFMA run; 1024: no priority
 // changes at all
-constexpr int CV_STAMPS = 10, CV_STAMP_WGS = 4096;   // [6..9] (ABL 256): K-loop cycles in vmcnt waits,
-                                                       // barriers, lgkmcnt waits, MFMA issue (wave 0)
+constexpr int CV_STAMPS = 16, CV_STAMP_WGS = 4096;   // [6..9] (ABL 256): K-loop cycles in vmcnt waits,
+                                                       // barriers, lgkmcnt waits, MFMA issue (wave 0) of
+                                                       // the steps of taps 1..8; [10..13]: of the tap-0 steps;
+                                                       // [14] / [15]: whole steps of taps 1..8 / tap 0
 __device__ unsigned long long g_cv3_stamp[CV_STAMP_WGS * CV_STAMPS];
 template <typename K_, bool RELU, int BN, int EPI, int ABL = 0, int TH = 16>
 __global__ void __launch_bounds__(512, 1) gemm_cv3_kernel(const GemmP p) {
@@ -126,6 +128,13 @@ __global__ void __launch_bounds__(512, 1) gemm_cv3_kernel(const GemmP p) {
     #pragma unroll
     for (int i = 0; i < 2; ++i) glds16s(boff, p.B + (long long)(h * 128 + i * 64) * p.ldb + 64 * t, dst + i * 8192);
   };
+  auto issue_patch1 = [&](int cb, int buf, int i) {   // piece i of the wave's PPW patch pieces
+    int c0 = wave * PPW * 64 + lane;              // the lane's chunk of piece 0
+    asm volatile("" : "+v"(c0));
+    const int j = wave_u * PPW + i;                     // piece index in the patch image
+    const uint32_t dst = lds0 + ((!TIGHT || j < G::NREAL) ? buf * PSTRIDE + j * 1024 : G::TRASH);
+    glds16b(patch_off(i, c0) + cb * 128, a_rs, dst);
+  };
   auto issue_patch3 = [&](int cb, int buf, int i0) {   // half of the wave's PPW patch pieces
     int c0 = wave * PPW * 64 + lane;              // the lane's chunk of piece 0
     asm volatile("" : "+v"(c0));
@@ -191,6 +200,7 @@ __global__ void __launch_bounds__(512, 1) gemm_cv3_kernel(const GemmP p) {
       for (int fn = 0; fn < QF; ++fn)
         bf[qn][ks][fn] = __builtin_bit_cast(uint4, *(lds_u4*)((lds_c*)(uintptr_t)bbase[ks] + st * B_B + (qn * (TN / 2) + fn * 16) * 128));
   };
+  int so_ = 0;   // (ABL 256) stamp set of the current step: 4 in a tap-0 step
   auto tick = [&]() -> unsigned long long {
     if constexpr ((ABL & 256) != 0) return __builtin_amdgcn_s_memtime();
     return 0ull;
@@ -200,18 +210,8 @@ __global__ void __launch_bounds__(512, 1) gemm_cv3_kernel(const GemmP p) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     const unsigned long long m1_ = tick();
-    if constexpr ((ABL & 256) != 0) st_[8] += m1_ - m0_;
+    if constexpr ((ABL & 256) != 0) st_[8 + so_] += m1_ - m0_;
     if constexpr (ABL & 4) return;
-    // the ReLU prologue in place, once per fragment (its first use, qn = 0): no relu'd copies held
-    // beside the fragments, half the v_pk_max of a per-use ReLU
-    if constexpr (RELU && !(ABL & 32)) {
-      if (qn == 0) {
-        #pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-          #pragma unroll
-          for (int fm = 0; fm < HQ; ++fm) af[ks][fm] = relu_pk16(af[ks][fm]);
-      }
-    }
     if constexpr ((ABL & 1536) == 0) __builtin_amdgcn_s_setprio(1);
     #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
@@ -222,18 +222,33 @@ __global__ void __launch_bounds__(512, 1) gemm_cv3_kernel(const GemmP p) {
           acc[qm * HQ + fm][qn * QF + fn] = K_::mfma16(bf[qn][ks][fn], af[ks][fm], acc[qm * HQ + fm][qn * QF + fn]);
       }
     if constexpr ((ABL & 1536) == 0) __builtin_amdgcn_s_setprio(0);
-    if constexpr ((ABL & 256) != 0) { __builtin_amdgcn_sched_barrier(0); st_[9] += tick() - m1_; }
+    if constexpr ((ABL & 256) != 0) { __builtin_amdgcn_sched_barrier(0); st_[9 + so_] += tick() - m1_; }
+  };
+  // (RELU) the prologue ReLU in the read half of the phase: after the phase's fragment reads and
+  // LDS-DMA are issued, behind a counted wait for the A fragments alone (read first; the compiler's
+  // own lgkmcnt), in place, once per fragment -- not between the barrier and the MFMA run, where
+  // its 8 HQ v_pk_max held the MFMA pipe idle (768^2 ReLU conv 571 -> 542 us alone,
+  // profiles/r07a_cv3_dma_spread/)
+  auto relu_early = [&]() __attribute__((always_inline)) {
+    if constexpr (RELU && !(ABL & 32)) {
+      __builtin_amdgcn_sched_barrier(0);
+      #pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+        #pragma unroll
+        for (int fm = 0; fm < HQ; ++fm) af[ks][fm] = relu_pk16(af[ks][fm]);
+      __builtin_amdgcn_sched_barrier(0);
+    }
   };
   auto bar = [&]() {
     const unsigned long long b0_ = tick();
     if constexpr ((ABL & 16) == 0) asm volatile("s_barrier" ::: "memory");
-    if constexpr ((ABL & 256) != 0) st_[7] += tick() - b0_;
+    if constexpr ((ABL & 256) != 0) st_[7 + so_] += tick() - b0_;
   };
 
   // K loop: per K step (channel block cb, tap) two half-step phases {fragment reads, LDS-DMA,
   // s_barrier, MFMAs, s_barrier}; wave rows staggered by a barrier; weight step t+2 streamed in
-  // phase 1 (its stage's reads ended in phase 0), the next block's patch in phase 0 of a block's
-  // first step; one counted wait per step (phase 1) for step t+1.
+  // phase 1 (its stage's reads ended in phase 0), the next block's patch one piece per wave and
+  // step in phase 0 of the block's first PPW steps; one counted wait per step (phase 1) for step t+1.
   // prologue: patch of block 0 and weight steps 0 and 1
   issue_patch3(0, 0, 0); issue_patch3(0, 0, PPW / 2);
   #pragma unroll
@@ -260,26 +275,45 @@ __global__ void __launch_bounds__(512, 1) gemm_cv3_kernel(const GemmP p) {
     for (int tap = 0; tap < 9; ++tap) {
       const int ky = tap / 3, kx = tap - ky * 3, st = (ST0 + tap) & 1;
       const int t = cb * 9 + tap;
-      const bool np = tap == 0 && nb;             // this step streams the next block's patch
+      const bool np = tap < PPW && nb;            // this step streams piece `tap` of the next block's patch
       const bool n2 = t + 2 < KT;
+      if constexpr ((ABL & 256) != 0) so_ = tap == 0 ? 4 : 0;
+      const unsigned long long s0_ = tick();
       // two half-step phases (A rows qm, both column halves: 16 MFMAs per wave at BN 128, 32 at
       // BN 256) instead of four quadrant phases -- half the barriers per step (head.0c 449 / 453
       // -> 433 / 421 us, the 768^2 ResidualBlock convs 676 / 684 -> 642 / 629 us in-frame,
       // profiles/r03af_cv3_bn128_2phase/, r03ag_cv3_2phase/).  Phase 0 reads the step's weights
-      // and streams the next block's patch (its buffer was last read one phase earlier by the
-      // wave row behind); phase 1 streams weight step t+2 into this step's stage (read in
-      // phase 0), waits for step t+1, then issues the second weight half.
+      // and streams one piece of the next block's patch (taps 0 .. PPW-1; the other patch buffer was
+      // last read in the block before, at the latest one phase earlier by the wave row behind);
+      // phase 1 streams weight step t+2 into this step's stage (read in phase 0), waits for step
+      // t+1, then issues the second weight half.  One piece per step instead of all PPW in tap 0:
+      // that step's burst held both wave rows at its barriers (profiles/r07a_cv3_dma_spread/).
+      //
+      // vmcnt accounting (per wave, retired in issue order; W = 2 pieces = a weight half, P = a
+      // patch piece; NBH = 2, at NBH = 1 there is no second half):
+      //   step t        issued, oldest first, at the wait            wait   left in flight
+      //   tap < PPW     [W W](t+1)  P(tap)  W(t+2, half 0)           3      P, W(t+2, half 0)
+      //   other taps    [W W](t+1)  W(t+2, half 0)                   2      W(t+2, half 0)
+      //   t + 2 >= KT   [W W](t+1)  (no patch: the last block)       0
+      // (tap < PPW with t + 2 >= KT cannot happen: a next block means 9 more steps; the 1 is kept
+      // for the ablation builds.)  Piece P(tap) is older than W(t+2), so the wait of step t+1
+      // retires it: the last piece (tap PPW-1 <= 7) is complete after tap 8's wait at the latest,
+      // two barriers before the next block's first fragment read (the stagger of the wave rows
+      // needs one barrier more than the wait's own).
       readA(0, ky, kx, pb); readB(0, st); readB(1, st);
-      if (np && !(ABL & 2) && !(ABL & 128)) { issue_patch3(cb + 1, pb ^ 1, 0); issue_patch3(cb + 1, pb ^ 1, PPW / 2); }
+      if (np && !(ABL & 2) && !(ABL & 128)) issue_patch1(cb + 1, pb ^ 1, tap);
+      relu_early();
       bar(); mma(0, 0); mma(0, 1); bar();
       readA(1, ky, kx, pb);
       if (n2 && !(ABL & 2) && !(ABL & 64)) issue_b(0, t + 2);
+      relu_early();
       const unsigned long long v0_ = tick();
-      if (np) { if (n2) wait_vmcnt<PPW + 2>(); else wait_vmcnt<PPW>(); }
+      if (np) { if (n2) wait_vmcnt<1 + 2>(); else wait_vmcnt<1>(); }
       else { if (n2) wait_vmcnt<2>(); else wait_vmcnt<0>(); }
-      if constexpr ((ABL & 256) != 0) st_[6] += tick() - v0_;
+      if constexpr ((ABL & 256) != 0) st_[6 + so_] += tick() - v0_;
       if (NBH == 2 && n2 && !(ABL & 2) && !(ABL & 64)) issue_b(1, t + 2);
       bar(); mma(1, 0); mma(1, 1); bar();
+      if constexpr ((ABL & 256) != 0) st_[tap == 0 ? 15 : 14] += tick() - s0_;
     }
     // the next block reads the other patch buffer
     if constexpr (!TIGHT) {
@@ -480,7 +514,9 @@ int launch_cv3(const GemmP& p0, hipStream_t s, int th) {
   // value without a variant runs the normal kernel
   const int abl = (p.dbg & (1 << 24)) ? p.dbg & 2047 : 0;
   if (th == 24) {   // 24 x 16-pixel tiles, 128 channels: 2 x 64 KiB patches + 2 x 16 KiB weight steps
-    if (epi == CV_EPI_HPS) hipLaunchKernelGGL((gemm_cv3_kernel<K_, false, 128, CV_EPI_HPS, 0, 24>), grid, dim3(512), 0, s, p);
+    if (epi == CV_EPI_BC && !p.relu_a && abl == 8) hipLaunchKernelGGL((gemm_cv3_kernel<K_, false, 128, CV_EPI_BC, 8, 24>), grid, dim3(512), 0, s, p);
+    else if (epi == CV_EPI_BC && !p.relu_a && abl == 264) hipLaunchKernelGGL((gemm_cv3_kernel<K_, false, 128, CV_EPI_BC, 264, 24>), grid, dim3(512), 0, s, p);
+    else if (epi == CV_EPI_HPS) hipLaunchKernelGGL((gemm_cv3_kernel<K_, false, 128, CV_EPI_HPS, 0, 24>), grid, dim3(512), 0, s, p);
     else if (p.relu_a) hipLaunchKernelGGL((gemm_cv3_kernel<K_, true, 128, CV_EPI_BC, 0, 24>), grid, dim3(512), 0, s, p);
     else hipLaunchKernelGGL((gemm_cv3_kernel<K_, false, 128, CV_EPI_BC, 0, 24>), grid, dim3(512), 0, s, p);
     DP_CHECK_LAUNCH();

@@ -41,7 +41,7 @@ enum { DP_A_DENSE = 0, DP_A_CONV = 1 };
 enum { DP_STORE_ROWS = 0, DP_STORE_DECONV2X2 = 1, DP_STORE_HEAD_PS = 2 };
 
 /* ABI version of this header; the Python loader refuses a mismatching .so. */
-#define DP_ABI_VERSION 19
+#define DP_ABI_VERSION 20
 int dp_abi_version(void);
 
 /*
@@ -945,6 +945,128 @@ int dp_knn_search(const double* points, const int32_t* n_dev, int32_t n_max, dou
 int dp_estimate_normals(const double* points, const int32_t* n_dev, int32_t n_max, const int32_t* nbr,
                         const int32_t* nbr_count, int32_t max_nn, const double* camera, int32_t orient,
                         double* normals_out, double* stats_out, dp_stream_t stream);
+
+/*
+ * ---- Occupancy floor plan (ABI 20, csrc/dp_floorplan.hip) ------------------------------------------
+ * The reference's second floor-plan output, cleaned_pointcloud_to_floorplan.py, up to the contour
+ * tracing: the top-down density grid (create_density_grid_from_points :172-212, create_direct_floorplan
+ * :676-886), the morphological closing and opening of process_height_slice (:245-311: closing 7 x 7
+ * twice, opening 3 x 3), the connected regions the reference then outlines, and a picture.  The ground,
+ * clean and cluster sections' conventions hold: fp64 points [n_max][3], n_dev a device int32 (NULL:
+ * n_max; clamped to [0, n_max]), everything on the caller's stream with no synchronisation and no host
+ * read-back, each fp64 product, sum and difference rounded on its own (no FMA), argument errors returned
+ * as DP_ERR_* before any launch.
+ * The grid's size is only known on the device.  Grid buffers have the caller's capacity max_cells (in
+ * [0, 2^31 - 1]); dims is a device int32 [2] = (H, W), written by dp_occupancy_grid and read ON THE DEVICE
+ * by every later stage -- it is their live count, as n_dev is the raster's.  A dims outside [0,
+ * DP_FLOOR_MAX_DIM] or with H * W > max_cells is read as (0, 0).  Grids are row-major, cell = gz * W + gx,
+ * row 0 = smallest z; cells at or beyond H * W are neither read nor written.
+ *   workspace  >= dp_floorplan_workspace_size(max_cells, max_regions) bytes of device memory, 8-byte
+ *              aligned, owned by the call until the stream has passed it (content need not be
+ *              initialised).  About 13.3 bytes per cell and 96 per region.  dp_occupancy_grid and
+ *              dp_grid_morphology need dp_floorplan_workspace_size(max_cells, 0) only.
+ * OpenCV is not available to check against; the rules below are the specification (restated in
+ * tests/floorplan_numpy.py, which is pinned to scipy.ndimage).
+ *
+ * Raster (dp_occupancy_grid).
+ *   1. Participants: the finite live rows with y >= height_threshold; a NaN threshold takes every finite
+ *      row (an infinite one: DP_ERR_SHAPE).
+ *   2. Coordinates are x and z as stored.  The picture does NOT take the x flip (u = -x) of the shapes
+ *      stage: it is the reference's imshow of its own grid, which has none.
+ *   3. min_x = (minimum of x over the participants) - padding, max_x = (maximum) + padding, the same for
+ *      z.  W = (int)ceil((max_x - min_x) / resolution), H from z (create_density_grid_from_points).
+ *      origin_out, fp64 [2] on the device = (min_x, min_z).
+ *   4. A participant's cell: gx = (int)((x - min_x) / resolution), gz likewise.  A row with gx >= W or
+ *      gz >= H is dropped and counted (with padding = 0 the row on the maximum is: the reference drops
+ *      it too).
+ *   5. Per cell:  density_out  uint32: the number of its members;
+ *                 height_out   float32: the largest (float)y of its members, 0 in an empty cell (-0.0
+ *                              counts as +0.0);
+ *                 color_out    uint8 [3] (colors != NULL): the colour of the member with the largest
+ *                              (float)y, among equal heights the smallest row; not written in an empty
+ *                              cell;
+ *                 occupied_out uint8: density > 0.
+ *   6. stats_out fp64 [8]: participants, non-finite rows, finite rows below the threshold, dropped rows,
+ *      occupied cells, H, W, error.  Error 1: no participants.  Error 2: W or H exceeds
+ *      DP_FLOOR_MAX_DIM, or W * H > max_cells.  Under either dims = (0, 0) and no cell is written
+ *      (origin is 0, 0 under error 1).
+ *   Stated differences: the reference's loop never colours a cell whose heights are all <= 0 and takes
+ *   the first of equal heights in its (randomly thinned) order; here every occupied cell has an owner and
+ *   ties go to the smallest row.  The reference thins the cloud at random in its fast mode; this uses
+ *   every participant.
+ *   Method: one pass for the minimum / maximum, one for the cells: a 64-bit atomicMax on (ordered float32
+ *   bits of y) << 32 | ~row gives height and colour owner at once, beside an atomicAdd on the density; a
+ *   wave first joins the rows that share a cell (they mostly do: the cloud is in image order), so a dense
+ *   cell takes one atomic pair per wave, not per row.
+ *   resolution not finite or <= 0, padding not finite or < 0: DP_ERR_SHAPE.
+ *
+ * Morphology (dp_grid_morphology): cv2.morphologyEx on the binary grid (non-zero = set; the output is 0 / 1).
+ *   7. close_iters times: a dilation, then an erosion, by a close_size x close_size square of ones; then
+ *      once: an erosion, then a dilation, by open_size x open_size.  Sizes are odd and in [1,
+ *      DP_FLOOR_MAX_KERNEL] (else DP_ERR_SHAPE); size 1, or 0 iterations, is the identity.
+ *   8. Border (OpenCV's default): a dilation reads the cells outside the grid as 0, an erosion reads them
+ *      as 1: scipy.ndimage.binary_dilation(border_value=0) and binary_erosion(border_value=1) with the
+ *      same structure.  (ndimage.binary_closing itself erodes with border 0 and is not the same.)
+ *   grid_out may be grid.
+ *   Method: rows packed 64 cells to a word by a wave's ballot; a square of ones is separable: the row pass
+ *   is shifts of a word and its two neighbours ORed / ANDed, the column pass ORs / ANDs k row words.  No LDS.
+ *
+ * Regions (dp_grid_regions): the 8-connected components of a uint8 grid (non-zero = set) and their table.
+ *   9. labels_out int32 [max_cells]: 0 on background; components numbered from 1 in row-major order of
+ *      their first cell -- scipy.ndimage.label(structure = ones((3, 3))).
+ *  10. n_regions_dev, device int32: the number of regions.  table_out fp64 [max_regions]
+ *      [DP_FLOOR_COLUMNS], rows r < min(regions, max_regions) written, row r for label r + 1:
+ *        0 cells; 1 area in m^2 = cells * (resolution * resolution); 2..5 bounding box gx0, gz0, gx1, gz1
+ *        (inclusive); 6, 7 centroid in cells: (sum of gx) / cells, (sum of gz) / cells, the sums exact
+ *        (64-bit integers), one division each; 8, 9 centroid in world coordinates origin + (c + 0.5) *
+ *        resolution; 10 points: the sum of density over the region; 11 the largest height over the
+ *        region's cells with density > 0 (0 if none); 12 the mean of height over those cells (0 if none):
+ *        an fp64 sum in an unspecified order, divided by their number.
+ *      A region past max_regions keeps its label but has no row.
+ *  11. stats_out fp64 [8]: set cells, regions, rows written, overflow flag (regions > max_regions), H, W,
+ *      0, 0.
+ *   density and height are the raster's (or any arrays of that layout); origin is its origin_out.
+ *   Method: union-find over the cell index (dp_points.h: hook the larger root under the smaller, path
+ *   halving), each cell joined to its west, north-west, north and north-east neighbours; the root of a
+ *   region is then its first cell, and a scan of the root flags numbers them.  The table is accumulated
+ *   with 64-bit integer atomics (one fp64 atomic for the height sum).
+ *   Bounds: no kernel waits on another workgroup; a find walks at most the chain to its root, which
+ *   halving keeps short but which is not bounded below the region's size.
+ *   Stated difference: the reference measures a region by cv2.contourArea of its traced outline and
+ *   drops those of 5 or less; here the area is the cell count.  findContours, approxPolyDP, the polygons
+ *   file and detect_and_split_l_shapes are not built.
+ *
+ * Picture (dp_floorplan_image): image_out uint8 [max_cells][3], RGB, H x W as the grids (row 0 = smallest z).
+ *  12. White background.  A cell whose label has a table row with area >= min_area is filled; the cells
+ *      of every other region (too small, or past max_regions) are background.
+ *  13. Fill colour, with color_by_height: h = min(1, mean / max_height) from the row's mean height,
+ *      r = (int)(255 h), g = (int)(255 (1 - |2h - 1|)), b = (int)(255 (1 - h)), each saturated to [0, 255]
+ *      (as OpenCV does with a colour tuple; only a negative mean needs it).  Without: grey 180.
+ *  14. A filled cell with a 4-neighbour outside the grid or of another label is black (the outline).
+ *  15. The reference's 1 m scale bar with its non-fast sizes: L = (int)(1 / resolution), x0 = min(W - 50 - L,
+ *      W - 10), z0 = min(H - 50, H - 10); if x0 > 0, z0 > 0, z0 < H and x0 + L < W the cells
+ *      [z0, z0 + 20) x [x0, x0 + L) inside the grid are black.  The Hershey title and "1m" text are not drawn.
+ *   min_area finite and >= 0, max_height and resolution finite and > 0 (else DP_ERR_SHAPE).
+ */
+#define DP_FLOOR_MAX_DIM 8192
+#define DP_FLOOR_MAX_KERNEL 15
+#define DP_FLOOR_COLUMNS 13
+int64_t dp_floorplan_workspace_size(int64_t max_cells, int64_t max_regions);
+int dp_occupancy_grid(const double* points, const uint8_t* colors, const int32_t* n_dev, int32_t n_max,
+                      double height_threshold, double resolution, double padding, int32_t max_cells,
+                      uint32_t* density_out, float* height_out, uint8_t* color_out, uint8_t* occupied_out,
+                      int32_t* dims_out, double* origin_out, double* stats_out, void* workspace,
+                      int64_t workspace_bytes, dp_stream_t stream);
+int dp_grid_morphology(const uint8_t* grid, const int32_t* dims, int32_t max_cells, int32_t close_size,
+                       int32_t close_iters, int32_t open_size, uint8_t* grid_out, void* workspace,
+                       int64_t workspace_bytes, dp_stream_t stream);
+int dp_grid_regions(const uint8_t* grid, const uint32_t* density, const float* height, const int32_t* dims,
+                    const double* origin, int32_t max_cells, double resolution, int32_t max_regions,
+                    int32_t* labels_out, int32_t* n_regions_dev, double* table_out, double* stats_out,
+                    void* workspace, int64_t workspace_bytes, dp_stream_t stream);
+int dp_floorplan_image(const int32_t* labels, const int32_t* dims, int32_t max_cells, const double* table,
+                       const int32_t* n_regions_dev, int32_t max_regions, double resolution, double min_area,
+                       double max_height, int32_t color_by_height, uint8_t* image_out, dp_stream_t stream);
 
 #ifdef __cplusplus
 }

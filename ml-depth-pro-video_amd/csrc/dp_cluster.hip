@@ -226,31 +226,7 @@ __global__ void __launch_bounds__(256) core_kernel(const u64* __restrict__ keys,
   }
 }
 
-// ---- union-find over core points, in row-index space ---------------------------------------------
-// parent[i] <= i always: a root is only ever hooked under a smaller root (CAS on the root's own
-// word), and path halving only lowers a word to one of its ancestors (atomicMin).  So there are no
-// cycles, a find terminates, and when all unions are done every root is its set's smallest row.
-__device__ __forceinline__ uint32_t ld(const uint32_t* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
-__device__ __forceinline__ uint32_t uf_find(uint32_t* p, uint32_t i) {
-  uint32_t q = ld(&p[i]);
-  while (q != i) {
-    const uint32_t g = ld(&p[q]);
-    if (g != q) atomicMin(&p[i], g);
-    i = q;
-    q = g;
-  }
-  return i;
-}
-__device__ __forceinline__ void uf_unite(uint32_t* p, uint32_t a, uint32_t b) {
-  for (;;) {
-    a = uf_find(p, a);
-    b = uf_find(p, b);
-    if (a == b) return;
-    if (a < b) { const uint32_t t = a; a = b; b = t; }
-    if (atomicCAS(&p[a], a, b) == a) return;                     // lost: someone else hooked a; find again
-  }
-}
-
+// ---- union-find over core points, in row-index space (uf_find / uf_unite: dp_points.h) -----------
 // A dense cell joins all its points to its first one (the smallest row of the cell: the sort is
 // stable).  A neighbouring dense cell is one set already, so it is skipped when that set is the
 // point's own, and left at the first neighbour found in it.

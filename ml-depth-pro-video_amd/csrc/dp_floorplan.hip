@@ -1,0 +1,593 @@
+// Occupancy floor plan (ABI 20): the top-down raster of the levelled cloud, binary morphology with OpenCV's
+// border rule, 8-connected regions with their table, and the picture -- everything of the reference's
+// cleaned_pointcloud_to_floorplan.py in front of the contour tracing.  The specification is in dp_mi355x.h.
+// fp64 with no FMA contraction where coordinates are involved.  The grid's size is only known on the device
+// (dims), so every kernel is launched for the caller's capacity and strides over the cells that exist.
+#include "dp_common.h"
+#include "dp_points.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int GRID_CAP = 4096;                  // workgroups of a per-point or per-cell kernel at the most
+constexpr int MAX_DIM = DP_FLOOR_MAX_DIM;
+constexpr int COLS = DP_FLOOR_COLUMNS;
+constexpr int ACC = 12;                         // 64-bit accumulators per region (A_* below)
+enum { A_COUNT = 0, A_SX, A_SZ, A_POINTS, A_OCC, A_SUMH, A_X0, A_Z0, A_X1, A_Z1, A_MAXH };
+
+struct Hdr {
+  u64 mm[4];            // keys of min / max of x, z over the participants
+  uint32_t ctr[8];
+  double par[4];        // min_x, min_z, resolution
+  int32_t dim[2];       // H, W of the raster call (0, 0 under an error)
+  int32_t ncells;       // H * W of the regions call (the scan's live count)
+  int32_t pad;
+};
+enum { C_PART = 0, C_NONFINITE, C_BELOW, C_DROPPED, C_OCCUPIED, C_ERR, C_FG };
+
+// H, W as every later stage reads them: anything outside [0, MAX_DIM] or beyond the capacity is no grid
+__device__ __forceinline__ void grid_dims(const int32_t* dims, int max_cells, int& H, int& W) {
+  H = dims[0]; W = dims[1];
+  if (H < 0 || W < 0 || H > MAX_DIM || W > MAX_DIM || (long long)H * W > max_cells) { H = 0; W = 0; }
+}
+
+// float32 -> order-preserving 32 bits (-0.0 folded onto +0.0) and back
+__device__ __forceinline__ uint32_t okey32(float v) {
+  uint32_t b = __float_as_uint(v);
+  if (v == 0.0f) b = 0;
+  return (b >> 31) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float unkey32(uint32_t k) { return __uint_as_float((k >> 31) ? (k & 0x7fffffffu) : ~k); }
+
+// ---- raster ---------------------------------------------------------------------------------------
+__global__ void hdr_init_kernel(Hdr* h) {
+  for (int a = 0; a < 2; ++a) { h->mm[2 * a] = ~0ull; h->mm[2 * a + 1] = 0; }
+  for (int a = 0; a < 8; ++a) h->ctr[a] = 0;
+  for (int a = 0; a < 4; ++a) h->par[a] = 0.0;
+  h->dim[0] = h->dim[1] = 0;
+  h->ncells = 0;
+}
+
+__device__ __forceinline__ bool takes_part(double x, double y, double z, double thr, bool& finite) {
+  finite = finite3(x, y, z);
+  return finite && !(y < thr);                    // a NaN threshold takes every finite row
+}
+
+__global__ void __launch_bounds__(256) minmax_xz_kernel(const double* __restrict__ pts, const int32_t* n_dev, int n_max,
+                                                        double thr, Hdr* h) {
+  const int n = live_n(n_dev, n_max);
+  u64 mn[2] = {~0ull, ~0ull}, mx[2] = {0, 0};
+  uint32_t bad = 0, low = 0, good = 0;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    const double x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
+    bool finite;
+    if (!takes_part(x, y, z, thr, finite)) { bad += !finite; low += finite; continue; }
+    ++good;
+    const u64 k[2] = {okey(x), okey(z)};
+    #pragma unroll
+    for (int a = 0; a < 2; ++a) { mn[a] = k[a] < mn[a] ? k[a] : mn[a]; mx[a] = k[a] > mx[a] ? k[a] : mx[a]; }
+  }
+  #pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    wave_minmax(mn, mx, o);
+    bad += __shfl_xor(bad, o); low += __shfl_xor(low, o); good += __shfl_xor(good, o);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (good) {
+      flush_minmax(h->mm, mn, mx);
+      atomicAdd(&h->ctr[C_PART], good);
+    }
+    if (bad) atomicAdd(&h->ctr[C_NONFINITE], bad);
+    if (low) atomicAdd(&h->ctr[C_BELOW], low);
+  }
+}
+
+// cells along one axis: (int)ceil(((max + padding) - min) / resolution), or -1 for more than MAX_DIM (NaN included)
+__device__ __forceinline__ int axis_cells(double mn, double mx_padded, double res) {
+  const double c = __builtin_ceil((mx_padded - mn) / res);
+  return c >= 0.0 && c <= (double)MAX_DIM ? (int)c : -1;
+}
+
+__global__ void grid_setup_kernel(Hdr* h, double res, double padding, int max_cells, int32_t* dims, double* origin) {
+  int err = 0, H = 0, W = 0;
+  double ox = 0.0, oz = 0.0;
+  if (!h->ctr[C_PART]) {
+    err = 1;
+  } else {
+    ox = unkey(h->mm[0]) - padding;
+    oz = unkey(h->mm[2]) - padding;
+    W = axis_cells(ox, unkey(h->mm[1]) + padding, res);
+    H = axis_cells(oz, unkey(h->mm[3]) + padding, res);
+    if (W < 0 || H < 0 || (long long)W * H > max_cells) { err = 2; H = 0; W = 0; }
+  }
+  h->par[0] = ox; h->par[1] = oz; h->par[2] = res;
+  h->dim[0] = dims[0] = H;
+  h->dim[1] = dims[1] = W;
+  h->ctr[C_ERR] = (uint32_t)err;
+  origin[0] = ox; origin[1] = oz;
+}
+
+__global__ void __launch_bounds__(256) grid_clear_kernel(const Hdr* h, u64* __restrict__ keys, uint32_t* __restrict__ density) {
+  const long long cells = (long long)h->dim[0] * h->dim[1];
+  for (long long c = (long long)blockIdx.x * 256 + threadIdx.x; c < cells; c += (long long)gridDim.x * 256) {
+    keys[c] = 0;
+    density[c] = 0;
+  }
+}
+
+// One row per lane.  The rows of a wave mostly fall into a few cells (the cloud is in image order), so the
+// wave first joins its rows cell by cell: the lanes of the first pending lane's cell add their number and
+// the largest of their keys with one atomic each, until no lane is pending.  The loop is wave-uniform.
+__global__ void __launch_bounds__(256) raster_kernel(const double* __restrict__ pts, const int32_t* n_dev, int n_max, double thr,
+                                                     Hdr* h, u64* __restrict__ keys, uint32_t* __restrict__ density) {
+  const int n = live_n(n_dev, n_max), lane = threadIdx.x & 63;
+  const int H = h->dim[0], W = h->dim[1];
+  if (h->ctr[C_ERR]) return;
+  const double ox = h->par[0], oz = h->par[1], res = h->par[2];
+  uint32_t dropped = 0;
+  for (long long base = ((long long)blockIdx.x * 256 + (threadIdx.x & ~63)); base < n; base += (long long)gridDim.x * 256) {
+    const long long i = base + lane;
+    bool valid = false;
+    int cell = -1;
+    u64 key = 0;
+    if (i < n) {
+      const double x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
+      bool finite;
+      if (takes_part(x, y, z, thr, finite)) {
+        const double qx = (x - ox) / res, qz = (z - oz) / res;        // >= 0: ox, oz lie at or below every participant
+        if (qx < (double)W && qz < (double)H) {
+          cell = (int)qz * W + (int)qx;
+          key = ((u64)okey32((float)y) << 32) | (u64)(~(uint32_t)i);
+          valid = true;
+        } else {
+          ++dropped;
+        }
+      }
+    }
+    u64 todo = __ballot(valid);
+    while (todo) {
+      const int leader = __ffsll((long long)todo) - 1;
+      const int lc = __shfl(cell, leader);
+      const bool mine = valid && cell == lc;
+      const u64 m = __ballot(mine);
+      u64 k = mine ? key : 0;
+      #pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const u64 t = __shfl_xor(k, o);
+        k = t > k ? t : k;
+      }
+      if (lane == leader) {
+        atomicAdd(&density[lc], (uint32_t)__popcll(m));
+        atomicMax(&keys[lc], k);
+      }
+      todo &= ~m;
+    }
+  }
+  #pragma unroll
+  for (int o = 32; o > 0; o >>= 1) dropped += __shfl_xor(dropped, o);
+  if (lane == 0 && dropped) atomicAdd(&h->ctr[C_DROPPED], dropped);
+}
+
+__global__ void __launch_bounds__(256) grid_finish_kernel(Hdr* h, const u64* __restrict__ keys, const uint32_t* __restrict__ density,
+                                                          const uint8_t* __restrict__ colors, int n_max, float* __restrict__ height,
+                                                          uint8_t* __restrict__ color, uint8_t* __restrict__ occupied) {
+  const long long cells = (long long)h->dim[0] * h->dim[1];
+  for (long long b = (long long)blockIdx.x * 256; b < cells; b += (long long)gridDim.x * 256) {
+    const long long c = b + threadIdx.x;
+    bool occ = false;
+    if (c < cells) {
+      const u64 k = keys[c];
+      occ = density[c] > 0;
+      height[c] = occ ? unkey32((uint32_t)(k >> 32)) : 0.0f;
+      occupied[c] = occ;
+      if (color && occ) {
+        const size_t row = row_of(~(uint32_t)k, n_max);
+        color[3 * c] = colors[3 * row]; color[3 * c + 1] = colors[3 * row + 1]; color[3 * c + 2] = colors[3 * row + 2];
+      }
+    }
+    wave_count(&h->ctr[C_OCCUPIED], occ);
+  }
+}
+
+__global__ void grid_stats_kernel(const Hdr* h, double* st) {
+  st[0] = (double)h->ctr[C_PART];
+  st[1] = (double)h->ctr[C_NONFINITE];
+  st[2] = (double)h->ctr[C_BELOW];
+  st[3] = (double)h->ctr[C_DROPPED];
+  st[4] = (double)h->ctr[C_OCCUPIED];
+  st[5] = (double)h->dim[0];
+  st[6] = (double)h->dim[1];
+  st[7] = (double)h->ctr[C_ERR];
+}
+
+// ---- morphology -----------------------------------------------------------------------------------
+// A row is packed 64 cells to a word, bit i of word j = cell 64 j + i; the bits past W in a row's last
+// word are kept 0.  One wave packs one word: the ballot of "my cell is set".
+__device__ __forceinline__ u64 tail_mask(int W) { return (W & 63) ? ((1ull << (W & 63)) - 1) : ~0ull; }
+
+__global__ void __launch_bounds__(256) pack_kernel(const uint8_t* __restrict__ grid, const int32_t* dims, int max_cells,
+                                                   u64* __restrict__ bits) {
+  int H, W;
+  grid_dims(dims, max_cells, H, W);
+  const int WW = (W + 63) >> 6, lane = threadIdx.x & 63;
+  const long long words = (long long)H * WW;
+  for (long long t = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); t < words; t += (long long)gridDim.x * 4) {
+    const int r = (int)(t / WW), gx = (int)(t % WW) * 64 + lane;
+    const u64 w = __ballot(gx < W && grid[(long long)r * W + gx] != 0);
+    if (lane == 0) bits[t] = w;
+  }
+}
+
+__global__ void __launch_bounds__(256) unpack_kernel(const u64* __restrict__ bits, const int32_t* dims, int max_cells,
+                                                     uint8_t* __restrict__ grid) {
+  int H, W;
+  grid_dims(dims, max_cells, H, W);
+  const int WW = (W + 63) >> 6;
+  const long long cells = (long long)H * W;
+  for (long long c = (long long)blockIdx.x * 256 + threadIdx.x; c < cells; c += (long long)gridDim.x * 256) {
+    const int r = (int)(c / W), gx = (int)(c % W);
+    grid[c] = (uint8_t)((bits[(long long)r * WW + (gx >> 6)] >> (gx & 63)) & 1);
+  }
+}
+
+// Horizontal pass of a (2 rad + 1)-wide row of ones, one thread per word: shifts of the word and its two
+// neighbours, ORed (dilation: cells outside the grid read 0) or ANDed (erosion: they read 1).
+__global__ void __launch_bounds__(256) morph_h_kernel(const u64* __restrict__ src, u64* __restrict__ dst, const int32_t* dims,
+                                                      int max_cells, int rad, int erode) {
+  int H, W;
+  grid_dims(dims, max_cells, H, W);
+  const int WW = (W + 63) >> 6;
+  const long long words = (long long)H * WW;
+  const u64 fill = erode ? ~0ull : 0ull, tail = tail_mask(W);
+  for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < words; t += (long long)gridDim.x * 256) {
+    const int j = (int)(t % WW);
+    u64 C = src[t];
+    if (j == WW - 1) C = (C & tail) | (fill & ~tail);
+    const u64 L = j > 0 ? src[t - 1] : fill;
+    u64 R = fill;
+    if (j + 1 < WW) {
+      R = src[t + 1];
+      if (j + 1 == WW - 1) R = (R & tail) | (fill & ~tail);
+    }
+    u64 acc = C;
+    for (int s = 1; s <= rad; ++s) {
+      const u64 a = (C >> s) | (R << (64 - s)), b = (C << s) | (L >> (64 - s));
+      acc = erode ? (acc & a & b) : (acc | a | b);
+    }
+    dst[t] = j == WW - 1 ? (acc & tail) : acc;
+  }
+}
+
+// Vertical pass: OR / AND over the 2 rad + 1 row words; a row outside the grid is the neutral element.
+__global__ void __launch_bounds__(256) morph_v_kernel(const u64* __restrict__ src, u64* __restrict__ dst, const int32_t* dims,
+                                                      int max_cells, int rad, int erode) {
+  int H, W;
+  grid_dims(dims, max_cells, H, W);
+  const int WW = (W + 63) >> 6;
+  const long long words = (long long)H * WW;
+  for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < words; t += (long long)gridDim.x * 256) {
+    const int r = (int)(t / WW);
+    u64 acc = src[t];
+    for (int d = -rad; d <= rad; ++d) {
+      const int rr = r + d;
+      if (d == 0 || rr < 0 || rr >= H) continue;
+      const u64 w = src[t + (long long)d * WW];
+      acc = erode ? (acc & w) : (acc | w);
+    }
+    dst[t] = acc;
+  }
+}
+
+// ---- regions --------------------------------------------------------------------------------------
+constexpr uint32_t NO_CELL = ~0u;
+
+__global__ void __launch_bounds__(256) uf_init_kernel(const uint8_t* __restrict__ grid, const int32_t* dims, int max_cells,
+                                                      uint32_t* __restrict__ parent, Hdr* h) {
+  int H, W;
+  grid_dims(dims, max_cells, H, W);
+  const long long cells = (long long)H * W;
+  if (blockIdx.x == 0 && threadIdx.x == 0) h->ncells = (int32_t)cells;
+  for (long long b = (long long)blockIdx.x * 256; b < cells; b += (long long)gridDim.x * 256) {
+    const long long c = b + threadIdx.x;
+    const bool fg = c < cells && grid[c] != 0;
+    if (c < cells) parent[c] = fg ? (uint32_t)c : NO_CELL;
+    wave_count(&h->ctr[C_FG], fg);
+  }
+}
+
+// Every foreground cell is joined to its foreground neighbours to the west, north-west, north and north-east:
+// each 8-connected pair is seen once, from its later cell.
+__global__ void __launch_bounds__(256) uf_link_kernel(const uint8_t* __restrict__ grid, const int32_t* dims, int max_cells,
+                                                      uint32_t* __restrict__ parent) {
+  int H, W;
+  grid_dims(dims, max_cells, H, W);
+  const long long cells = (long long)H * W;
+  for (long long c = (long long)blockIdx.x * 256 + threadIdx.x; c < cells; c += (long long)gridDim.x * 256) {
+    if (!grid[c]) continue;
+    const int r = (int)(c / W), x = (int)(c % W);
+    if (x > 0 && grid[c - 1]) uf_unite(parent, (uint32_t)c, (uint32_t)(c - 1));
+    if (r > 0) {
+      const long long up = c - W;
+      if (x > 0 && grid[up - 1]) uf_unite(parent, (uint32_t)c, (uint32_t)(up - 1));
+      if (grid[up]) uf_unite(parent, (uint32_t)c, (uint32_t)up);
+      if (x + 1 < W && grid[up + 1]) uf_unite(parent, (uint32_t)c, (uint32_t)(up + 1));
+    }
+  }
+}
+
+// after the last union: every cell points at its root (the region's first cell), and the roots are flagged
+__global__ void __launch_bounds__(256) uf_flatten_kernel(const Hdr* h, uint32_t* __restrict__ parent, uint8_t* __restrict__ flag) {
+  const long long cells = h->ncells;
+  for (long long c = (long long)blockIdx.x * 256 + threadIdx.x; c < cells; c += (long long)gridDim.x * 256) {
+    uint8_t f = 0;
+    if (ld(&parent[c]) != NO_CELL) {
+      const uint32_t r = uf_find(parent, (uint32_t)c);
+      if (r != (uint32_t)c) atomicMin(&parent[c], r);
+      else f = 1;
+    }
+    flag[c] = f;
+  }
+}
+
+// Third step of the root flags' scan (dp_points.h): a root's number is 1 + the roots before it.
+__global__ void __launch_bounds__(256) root_number_kernel(const uint8_t* __restrict__ flag, const Hdr* h, int max_cells,
+                                                          const uint32_t* __restrict__ bc, int32_t* __restrict__ num) {
+  __shared__ uint32_t wsum[4];
+  const int n = live_n(&h->ncells, max_cells);
+  const long long tile = (long long)blockIdx.x * SCAN_TILE;
+  uint32_t run = bc[blockIdx.x];
+  for (int r = 0; r < SCAN_ITEMS && tile + r * 256 < n; ++r) {
+    const long long t = tile + r * 256 + threadIdx.x;
+    const uint32_t f = t < n ? flag[t] : 0u;
+    uint32_t tot = 0;
+    const uint32_t excl = run + block_excl_scan(f, wsum, &tot);
+    if (f) num[t] = (int32_t)(excl + 1);
+    run += tot;
+  }
+}
+
+__global__ void acc_init_kernel(u64* __restrict__ acc, int max_regions) {
+  for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < (long long)max_regions * ACC; t += (long long)gridDim.x * 256) {
+    const int a = (int)(t % ACC);
+    acc[t] = (a == A_X0 || a == A_Z0) ? ~0ull : 0ull;
+  }
+}
+
+// labels (in place over the parents: a thread reads and writes its own cell's word only) and the regions'
+// accumulators, one atomic per column and cell
+__global__ void __launch_bounds__(256) label_kernel(const int32_t* dims, int max_cells, int32_t* __restrict__ labels,
+                                                    const int32_t* __restrict__ num, const uint32_t* __restrict__ density,
+                                                    const float* __restrict__ height, int max_regions, u64* __restrict__ acc) {
+  int H, W;
+  grid_dims(dims, max_cells, H, W);
+  const long long cells = (long long)H * W;
+  for (long long c = (long long)blockIdx.x * 256 + threadIdx.x; c < cells; c += (long long)gridDim.x * 256) {
+    const uint32_t root = ((const uint32_t*)labels)[c];
+    if (root == NO_CELL || root >= (uint32_t)cells) { labels[c] = 0; continue; }
+    const int32_t l = num[root];
+    labels[c] = l;
+    if (l < 1 || l > max_regions) continue;
+    u64* a = acc + (size_t)(l - 1) * ACC;
+    const u64 x = (u64)(c % W), z = (u64)(c / W);
+    atomicAdd(&a[A_COUNT], 1ull);
+    atomicAdd(&a[A_SX], x);
+    atomicAdd(&a[A_SZ], z);
+    atomicMin(&a[A_X0], x); atomicMax(&a[A_X1], x);
+    atomicMin(&a[A_Z0], z); atomicMax(&a[A_Z1], z);
+    const uint32_t d = density[c];
+    if (d) {
+      const float hc = height[c];
+      atomicAdd(&a[A_POINTS], (u64)d);
+      atomicAdd(&a[A_OCC], 1ull);
+      atomicAdd((double*)&a[A_SUMH], (double)hc);
+      atomicMax(&a[A_MAXH], (u64)okey32(hc));
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) table_kernel(const int32_t* n_regions, int max_regions, const u64* __restrict__ acc,
+                                                    const double* origin, double res, double* __restrict__ table) {
+  const int rows = table_rows(n_regions, max_regions);
+  for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < rows; t += (long long)gridDim.x * 256) {
+    const u64* a = acc + (size_t)t * ACC;
+    double* row = table + (size_t)t * COLS;
+    const double cnt = (double)a[A_COUNT];
+    const double cx = (double)a[A_SX] / cnt, cz = (double)a[A_SZ] / cnt;
+    row[0] = cnt;
+    row[1] = cnt * (res * res);
+    row[2] = (double)a[A_X0]; row[3] = (double)a[A_Z0]; row[4] = (double)a[A_X1]; row[5] = (double)a[A_Z1];
+    row[6] = cx; row[7] = cz;
+    row[8] = origin[0] + (cx + 0.5) * res;
+    row[9] = origin[1] + (cz + 0.5) * res;
+    row[10] = (double)a[A_POINTS];
+    row[11] = a[A_OCC] ? (double)unkey32((uint32_t)a[A_MAXH]) : 0.0;
+    row[12] = a[A_OCC] ? __longlong_as_double((long long)a[A_SUMH]) / (double)a[A_OCC] : 0.0;
+  }
+}
+
+__global__ void regions_stats_kernel(const Hdr* h, const int32_t* dims, int max_cells, const int32_t* n_regions, int max_regions,
+                                     double* st) {
+  int H, W;
+  grid_dims(dims, max_cells, H, W);
+  const int n = *n_regions;
+  st[0] = (double)h->ctr[C_FG];
+  st[1] = (double)n;
+  st[2] = (double)table_rows(n_regions, max_regions);
+  st[3] = n > max_regions ? 1.0 : 0.0;
+  st[4] = (double)H;
+  st[5] = (double)W;
+  st[6] = st[7] = 0.0;
+}
+
+// ---- picture --------------------------------------------------------------------------------------
+__device__ __forceinline__ uint8_t sat_u8(double v) { return (uint8_t)(v < 0.0 ? 0 : (v > 255.0 ? 255 : (int)v)); }
+
+__global__ void __launch_bounds__(256) image_kernel(const int32_t* __restrict__ labels, const int32_t* dims, int max_cells,
+                                                    const double* __restrict__ table, const int32_t* n_regions, int max_regions,
+                                                    double min_area, double max_height, int by_height, int bar_len,
+                                                    uint8_t* __restrict__ image) {
+  int H, W;
+  grid_dims(dims, max_cells, H, W);
+  const long long cells = (long long)H * W;
+  const int rows = table_rows(n_regions, max_regions);
+  // the reference's 1 m scale bar (its non-fast sizes: 20 cells high, 50 from the lower right corner)
+  const int bx = min(W - 50 - bar_len, W - 10), bz = min(H - 50, H - 10);
+  const bool bar = bx > 0 && bz > 0 && bz < H && bx + bar_len < W;
+  for (long long c = (long long)blockIdx.x * 256 + threadIdx.x; c < cells; c += (long long)gridDim.x * 256) {
+    const int z = (int)(c / W), x = (int)(c % W);
+    const int32_t l = labels[c];
+    uint8_t r = 255, g = 255, b = 255;
+    if (l >= 1 && l <= rows && table[(size_t)(l - 1) * COLS + 1] >= min_area) {
+      const bool edge = x == 0 || x == W - 1 || z == 0 || z == H - 1 || labels[c - 1] != l || labels[c + 1] != l ||
+                        labels[c - W] != l || labels[c + W] != l;
+      if (edge) {
+        r = g = b = 0;
+      } else if (!by_height) {
+        r = g = b = 180;
+      } else {
+        const double q = table[(size_t)(l - 1) * COLS + 12] / max_height;
+        const double hh = q < 1.0 ? q : 1.0;
+        r = sat_u8(255.0 * hh);
+        g = sat_u8(255.0 * (1.0 - __builtin_fabs(2.0 * hh - 1.0)));
+        b = sat_u8(255.0 * (1.0 - hh));
+      }
+    }
+    if (bar && z >= bz && z < bz + 20 && x >= bx && x < bx + bar_len) r = g = b = 0;
+    image[3 * c] = r; image[3 * c + 1] = g; image[3 * c + 2] = b;
+  }
+}
+
+// ---- workspace ------------------------------------------------------------------------------------
+struct Ws {
+  Hdr* h;
+  u64 *keys, *bits_a, *bits_b, *acc;
+  int32_t* num;
+  uint8_t* flag;
+  uint32_t* bc;
+};
+int64_t scan_blocks_for(int64_t n) { return (n + SCAN_TILE - 1) / SCAN_TILE; }
+// words of a packed grid: H * ceil(W / 64) <= (H W + 63 H) / 64
+int64_t bit_words_for(int64_t cells) { return cells / 64 + MAX_DIM + 1; }
+int64_t ws_bytes_for(int64_t max_cells, int64_t max_regions) {
+  const int64_t n = max_cells < 0 ? 0 : max_cells, k = max_regions < 0 ? 0 : max_regions;
+  return al256(sizeof(Hdr)) + al256(8 * n) + 2 * al256(8 * bit_words_for(n)) + al256(4 * n) + al256(n) +
+         al256(4 * (scan_blocks_for(n) + 1)) + al256(8 * ACC * k) + 256;
+}
+bool ws_carve(void* ws, int64_t bytes, int64_t max_cells, int64_t max_regions, Ws* o) {
+  if (!ws || bytes < ws_bytes_for(max_cells, max_regions) || ((uintptr_t)ws & 7)) return false;
+  const int64_t n = max_cells;
+  char* p = (char*)ws;
+  o->h = (Hdr*)p;            p += al256(sizeof(Hdr));
+  o->keys = (u64*)p;         p += al256(8 * n);
+  o->bits_a = (u64*)p;       p += al256(8 * bit_words_for(n));
+  o->bits_b = (u64*)p;       p += al256(8 * bit_words_for(n));
+  o->num = (int32_t*)p;      p += al256(4 * n);
+  o->flag = (uint8_t*)p;     p += al256(n);
+  o->bc = (uint32_t*)p;      p += al256(4 * (scan_blocks_for(n) + 1));
+  o->acc = (u64*)p;
+  return true;
+}
+bool pos_finite(double v) { return v > 0.0 && v < __builtin_inf(); }
+bool kernel_size_ok(int k) { return k >= 1 && k <= DP_FLOOR_MAX_KERNEL && (k & 1); }
+
+}  // namespace
+
+extern "C" int64_t dp_floorplan_workspace_size(int64_t max_cells, int64_t max_regions) { return ws_bytes_for(max_cells, max_regions); }
+
+extern "C" int dp_occupancy_grid(const double* points, const uint8_t* colors, const int32_t* n_dev, int32_t n_max,
+                                 double height_threshold, double resolution, double padding, int32_t max_cells,
+                                 uint32_t* density_out, float* height_out, uint8_t* color_out, uint8_t* occupied_out,
+                                 int32_t* dims_out, double* origin_out, double* stats_out, void* workspace,
+                                 int64_t workspace_bytes, dp_stream_t stream) {
+  if (!dims_out || !origin_out || !stats_out || (n_max > 0 && !points) || (colors && !color_out) ||
+      (max_cells > 0 && (!density_out || !height_out || !occupied_out)))
+    return DP_ERR_ARG;
+  if (n_max < 0 || max_cells < 0 || !pos_finite(resolution) || !(padding >= 0.0) || !(padding < __builtin_inf()) ||
+      __builtin_fabs(height_threshold) == __builtin_inf())
+    return DP_ERR_SHAPE;
+  Ws w;
+  if (!ws_carve(workspace, workspace_bytes, max_cells, 0, &w)) return DP_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const int gp = grid_for(n_max, GRID_CAP), gc = grid_for(max_cells, GRID_CAP);
+  hipLaunchKernelGGL(hdr_init_kernel, dim3(1), dim3(1), 0, s, w.h);
+  hipLaunchKernelGGL(minmax_xz_kernel, dim3(gp), dim3(256), 0, s, points, n_dev, n_max, height_threshold, w.h);
+  hipLaunchKernelGGL(grid_setup_kernel, dim3(1), dim3(1), 0, s, w.h, resolution, padding, max_cells, dims_out, origin_out);
+  hipLaunchKernelGGL(grid_clear_kernel, dim3(gc), dim3(256), 0, s, w.h, w.keys, density_out);
+  hipLaunchKernelGGL(raster_kernel, dim3(gp), dim3(256), 0, s, points, n_dev, n_max, height_threshold, w.h, w.keys, density_out);
+  hipLaunchKernelGGL(grid_finish_kernel, dim3(gc), dim3(256), 0, s, w.h, w.keys, density_out, colors, n_max, height_out,
+                     colors ? color_out : nullptr, occupied_out);
+  hipLaunchKernelGGL(grid_stats_kernel, dim3(1), dim3(1), 0, s, w.h, stats_out);
+  DP_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dp_grid_morphology(const uint8_t* grid, const int32_t* dims, int32_t max_cells, int32_t close_size,
+                                  int32_t close_iters, int32_t open_size, uint8_t* grid_out, void* workspace,
+                                  int64_t workspace_bytes, dp_stream_t stream) {
+  if (!dims || (max_cells > 0 && (!grid || !grid_out))) return DP_ERR_ARG;
+  if (max_cells < 0 || close_iters < 0 || !kernel_size_ok(close_size) || !kernel_size_ok(open_size)) return DP_ERR_SHAPE;
+  Ws w;
+  if (!ws_carve(workspace, workspace_bytes, max_cells, 0, &w)) return DP_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t words = bit_words_for(max_cells);
+  const int gw = grid_for(words, GRID_CAP), gc = grid_for(max_cells, GRID_CAP);
+  u64 *a = w.bits_a, *b = w.bits_b;
+  hipLaunchKernelGGL(pack_kernel, dim3(grid_for(64 * words, GRID_CAP)), dim3(256), 0, s, grid, dims, max_cells, a);
+  // one dilation or erosion by a (2 rad + 1)-square: the row pass, then the column pass
+  auto pass = [&](int rad, int erode) {
+    hipLaunchKernelGGL(morph_h_kernel, dim3(gw), dim3(256), 0, s, a, b, dims, max_cells, rad, erode);
+    hipLaunchKernelGGL(morph_v_kernel, dim3(gw), dim3(256), 0, s, b, a, dims, max_cells, rad, erode);
+  };
+  if (close_size > 1)
+    for (int it = 0; it < close_iters; ++it) { pass(close_size / 2, 0); pass(close_size / 2, 1); }
+  if (open_size > 1) { pass(open_size / 2, 1); pass(open_size / 2, 0); }
+  hipLaunchKernelGGL(unpack_kernel, dim3(gc), dim3(256), 0, s, a, dims, max_cells, grid_out);
+  DP_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dp_grid_regions(const uint8_t* grid, const uint32_t* density, const float* height, const int32_t* dims,
+                               const double* origin, int32_t max_cells, double resolution, int32_t max_regions,
+                               int32_t* labels_out, int32_t* n_regions_dev, double* table_out, double* stats_out,
+                               void* workspace, int64_t workspace_bytes, dp_stream_t stream) {
+  if (!dims || !origin || !n_regions_dev || !stats_out || (max_regions > 0 && !table_out) ||
+      (max_cells > 0 && (!grid || !density || !height || !labels_out)))
+    return DP_ERR_ARG;
+  if (max_cells < 0 || max_regions < 0 || !pos_finite(resolution)) return DP_ERR_SHAPE;
+  Ws w;
+  if (!ws_carve(workspace, workspace_bytes, max_cells, max_regions, &w)) return DP_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const int gc = grid_for(max_cells, GRID_CAP), nb = (int)scan_blocks_for(max_cells);
+  uint32_t* parent = (uint32_t*)labels_out;
+  hipLaunchKernelGGL(hdr_init_kernel, dim3(1), dim3(1), 0, s, w.h);
+  hipLaunchKernelGGL(uf_init_kernel, dim3(gc), dim3(256), 0, s, grid, dims, max_cells, parent, w.h);
+  hipLaunchKernelGGL(uf_link_kernel, dim3(gc), dim3(256), 0, s, grid, dims, max_cells, parent);
+  hipLaunchKernelGGL(uf_flatten_kernel, dim3(gc), dim3(256), 0, s, w.h, parent, w.flag);
+  if (nb) hipLaunchKernelGGL(scan_count_kernel, dim3(nb), dim3(256), 0, s, w.flag, &w.h->ncells, max_cells, w.bc);
+  hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(256), 0, s, w.bc, nb, (uint32_t*)n_regions_dev);   // the same bits
+  if (nb) hipLaunchKernelGGL(root_number_kernel, dim3(nb), dim3(256), 0, s, w.flag, w.h, max_cells, w.bc, w.num);
+  hipLaunchKernelGGL(acc_init_kernel, dim3(grid_for((int64_t)max_regions * ACC, GRID_CAP)), dim3(256), 0, s, w.acc, max_regions);
+  hipLaunchKernelGGL(label_kernel, dim3(gc), dim3(256), 0, s, dims, max_cells, labels_out, w.num, density, height,
+                     max_regions, w.acc);
+  hipLaunchKernelGGL(table_kernel, dim3(grid_for(max_regions, GRID_CAP)), dim3(256), 0, s, n_regions_dev, max_regions, w.acc,
+                     origin, resolution, table_out);
+  hipLaunchKernelGGL(regions_stats_kernel, dim3(1), dim3(1), 0, s, w.h, dims, max_cells, n_regions_dev, max_regions, stats_out);
+  DP_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dp_floorplan_image(const int32_t* labels, const int32_t* dims, int32_t max_cells, const double* table,
+                                  const int32_t* n_regions_dev, int32_t max_regions, double resolution, double min_area,
+                                  double max_height, int32_t color_by_height, uint8_t* image_out, dp_stream_t stream) {
+  if (!dims || !n_regions_dev || (max_regions > 0 && !table) || (max_cells > 0 && (!labels || !image_out))) return DP_ERR_ARG;
+  if (max_cells < 0 || max_regions < 0 || !pos_finite(resolution) || !pos_finite(max_height) || !(min_area >= 0.0) ||
+      !(min_area < __builtin_inf()))
+    return DP_ERR_SHAPE;
+  const double len = 1.0 / resolution;
+  const int bar_len = len < (double)(2 * MAX_DIM) ? (int)len : 2 * MAX_DIM;        // longer than any grid: no bar
+  hipLaunchKernelGGL(image_kernel, dim3(grid_for(max_cells, GRID_CAP)), dim3(256), 0, (hipStream_t)stream, labels, dims,
+                     max_cells, table, n_regions_dev, max_regions, min_area, max_height, color_by_height, bar_len, image_out);
+  DP_CHECK_LAUNCH();
+  return 0;
+}

@@ -1,4 +1,5 @@
-// What the point-cloud stages share (dp_ground.hip, dp_clean.hip, dp_cluster.hip, dp_shapes.hip): one
+// What the point-cloud stages share (dp_ground.hip, dp_clean.hip, dp_cluster.hip, dp_shapes.hip,
+// dp_normals.hip, dp_floorplan.hip): one
 // copy of every device and host helper that two or more of them use.  A helper with one user stays in
 // its file.  Everything is in an anonymous namespace, so each translation unit has its own copy of the
 // two kernels below.
@@ -105,6 +106,31 @@ __device__ __forceinline__ void wave_minmax(u64 (&mn)[A], u64 (&mx)[A], int o) {
 template <int A>
 __device__ __forceinline__ void flush_minmax(u64* dst, const u64 (&mn)[A], const u64 (&mx)[A]) {
   for (int a = 0; a < A; ++a) { atomicMin(&dst[2 * a], mn[a]); atomicMax(&dst[2 * a + 1], mx[a]); }
+}
+
+// ---- lock-free union-find over 32-bit indices (cluster rows, grid cells) ---------------------------
+// parent[i] <= i always: a root is only ever hooked under a smaller root (CAS on the root's own
+// word), and path halving only lowers a word to one of its ancestors (atomicMin).  So there are no
+// cycles, a find terminates, and when all unions are done every root is its set's smallest row.
+__device__ __forceinline__ uint32_t ld(const uint32_t* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
+__device__ __forceinline__ uint32_t uf_find(uint32_t* p, uint32_t i) {
+  uint32_t q = ld(&p[i]);
+  while (q != i) {
+    const uint32_t g = ld(&p[q]);
+    if (g != q) atomicMin(&p[i], g);
+    i = q;
+    q = g;
+  }
+  return i;
+}
+__device__ __forceinline__ void uf_unite(uint32_t* p, uint32_t a, uint32_t b) {
+  for (;;) {
+    a = uf_find(p, a);
+    b = uf_find(p, b);
+    if (a == b) return;
+    if (a < b) { const uint32_t t = a; a = b; b = t; }
+    if (atomicCAS(&p[a], a, b) == a) return;                     // lost: someone else hooked a; find again
+  }
 }
 
 // ---- exclusive scan of a byte flag in row order: per-tile counts, then one workgroup turns them into

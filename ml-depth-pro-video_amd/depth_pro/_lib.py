@@ -29,7 +29,8 @@ INTERP_MODES = {"bilinear": DP_INTERP_BILINEAR, "bicubic": DP_INTERP_BICUBIC}
  DP_TILE_CV3_192x256, DP_TILE_CV3_384x128) = range(24)
 DP_SEL_PERCENTILE, DP_SEL_KTH = 0, 1
 DP_GROUND_MAX_SEG, DP_GROUND_MAX_GRID = 1024, 32
-DP_ABI_VERSION = 19
+DP_FLOOR_MAX_DIM, DP_FLOOR_MAX_KERNEL, DP_FLOOR_COLUMNS = 8192, 15, 13
+DP_ABI_VERSION = 20
 
 _ERRORS = {1000: "DP_ERR_ARG", 1001: "DP_ERR_SHAPE", 1002: "DP_ERR_ALIGN", 1003: "DP_ERR_DTYPE"}
 
@@ -50,6 +51,7 @@ EXPORTS = (
     "dp_cluster_workspace_size", "dp_cluster_dbscan", "dp_cluster_table",
     "dp_shapes_workspace_size", "dp_cluster_shapes",
     "dp_normals_workspace_size", "dp_voxel_downsample", "dp_knn_search", "dp_estimate_normals",
+    "dp_floorplan_workspace_size", "dp_occupancy_grid", "dp_grid_morphology", "dp_grid_regions", "dp_floorplan_image",
 )
 
 
@@ -154,6 +156,11 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "dp_voxel_downsample": [vp, vp, vp, i32, f64, vp, vp, vp, vp, vp, vp, vp, i64, vp],
         "dp_knn_search": [vp, vp, i32, f64, i32, vp, vp, vp, vp, i64, vp],
         "dp_estimate_normals": [vp, vp, i32, vp, vp, i32, ctypes.POINTER(f64), i32, vp, vp, vp],
+        "dp_floorplan_workspace_size": [i64, i64],
+        "dp_occupancy_grid": [vp, vp, vp, i32, f64, f64, f64, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp],
+        "dp_grid_morphology": [vp, vp, i32, i32, i32, i32, vp, vp, i64, vp],
+        "dp_grid_regions": [vp, vp, vp, vp, vp, i32, f64, i32, vp, vp, vp, vp, vp, i64, vp],
+        "dp_floorplan_image": [vp, vp, i32, vp, vp, i32, f64, f64, f64, i32, vp, vp],
     }
     for name, argtypes in sig.items():
         fn = getattr(lib, name)
@@ -165,6 +172,7 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.dp_cluster_workspace_size.restype = ctypes.c_int64
     lib.dp_shapes_workspace_size.restype = ctypes.c_int64
     lib.dp_normals_workspace_size.restype = ctypes.c_int64
+    lib.dp_floorplan_workspace_size.restype = ctypes.c_int64
     lib.dp_gemm_debug_flags.argtypes = [ctypes.c_int]
     lib.dp_gemm_debug_flags.restype = ctypes.c_int
     ver = lib.dp_abi_version()

@@ -28,6 +28,11 @@ Oriented mesh points (the start of the reference's meshing step, `pointcloud_to_
 `voxel_downsample`, `knn_search`, `estimate_normals` and `oriented_points` (all three with the reference's
 values) -- csrc/dp_normals.hip, no Open3D, no host read-back; `write_ply_normals` / `read_ply_normals` are the
 PLY writer and reader for a cloud with normals.
+
+Occupancy floor plan (the reference's `cleaned_pointcloud_to_floorplan.py` up to its contour tracing):
+`occupancy_grid`, `grid_morphology`, `grid_regions`, `floorplan_image` and `floor_plan` (all four with the
+reference's height-threshold values) -- csrc/dp_floorplan.hip, no OpenCV, no host read-back;
+`floor_plan_summary` makes the one read-back.
 """
 
 from __future__ import annotations
@@ -937,6 +942,204 @@ def read_ply_normals(path: str) -> Tuple[np.ndarray, np.ndarray, Optional[np.nda
     dt = [("p", "<f8", 3), ("n", "<f8", 3)] + ([("c", "u1", 3)] if any("red" in l for l in lines) else [])
     rec = np.frombuffer(data[end:], dtype=dt, count=n)
     return rec["p"].copy(), rec["n"].copy(), (rec["c"].copy() if len(dt) == 3 else None)
+
+
+# ---- occupancy floor plan: raster, morphology, regions, picture (csrc/dp_floorplan.hip) -------------
+
+GRID_STATS = ("participants", "non_finite", "below_threshold", "dropped", "occupied_cells", "height", "width", "error")
+REGION_STATS = ("set_cells", "regions", "rows", "overflow", "height", "width", "reserved0", "reserved1")
+REGION_COLUMNS = ("cells", "area", "gx0", "gz0", "gx1", "gz1", "cx", "cz", "x", "z", "points", "max_height", "mean_height")
+FLOOR_MAX_DIM, FLOOR_MAX_KERNEL = _lib.DP_FLOOR_MAX_DIM, _lib.DP_FLOOR_MAX_KERNEL
+
+_FLOOR = "the occupancy floor plan runs on the ROCm device (csrc/dp_floorplan.hip)"
+
+
+def _check_floor(resolution=0.1, padding=0.0, height_threshold=1.3, max_cells=0, close_size=1, close_iters=0, open_size=1,
+                 min_area=0.0, max_height=1.0, max_regions=0) -> None:
+    if not (np.isfinite(float(resolution)) and float(resolution) > 0):
+        raise ValueError(f"resolution must be finite and > 0 (got {resolution})")
+    if not (np.isfinite(float(padding)) and float(padding) >= 0):
+        raise ValueError(f"padding must be finite and >= 0 (got {padding})")
+    if np.isinf(float(height_threshold)):
+        raise ValueError("height_threshold must be finite, or NaN for every height")
+    if not 0 <= int(max_cells) < 2 ** 31 or not 0 <= int(max_regions) < 2 ** 31:
+        raise ValueError("max_cells and max_regions must be in [0, 2^31 - 1]")
+    for name, k in (("close_size", close_size), ("open_size", open_size)):
+        if not (1 <= int(k) <= FLOOR_MAX_KERNEL and int(k) % 2 == 1):
+            raise ValueError(f"{name} must be odd and in [1, {FLOOR_MAX_KERNEL}] (got {k})")
+    if int(close_iters) < 0:
+        raise ValueError(f"close_iters must be >= 0 (got {close_iters})")
+    if not (np.isfinite(float(min_area)) and float(min_area) >= 0):
+        raise ValueError(f"min_area must be finite and >= 0 (got {min_area})")
+    if not (np.isfinite(float(max_height)) and float(max_height) > 0):
+        raise ValueError(f"max_height must be finite and > 0 (got {max_height})")
+
+
+def _grid_args(grid: torch.Tensor, dims: torch.Tensor, dtype=torch.uint8, what: str = "grid"):
+    """(lib, flat contiguous grid, capacity in cells, stream) of a grid stage; `dims` is the device (H, W)."""
+    if grid.device.type != "cuda":
+        raise _lib.DPError(_FLOOR)
+    if grid.dtype != dtype:
+        raise ValueError(f"{what} must be a {dtype} tensor")
+    if not torch.is_tensor(dims) or dims.device != grid.device or dims.dtype != torch.int32 or dims.numel() != 2:
+        raise ValueError("dims must be a device int32 tensor (H, W) on the grid's device")
+    g = grid.contiguous().reshape(-1)
+    if g.numel() >= 2 ** 31:
+        raise ValueError("at most 2^31 - 1 cells")
+    return _lib.load(), g, g.numel(), torch.cuda.current_stream(g.device).cuda_stream
+
+
+def grid_dims(shape, device) -> torch.Tensor:
+    """A device `dims` for a grid made on the host: int32 (H, W)."""
+    h, w = (int(v) for v in shape)
+    return torch.tensor([h, w], dtype=torch.int32, device=device)
+
+
+def occupancy_grid(points: torch.Tensor, colors: Optional[torch.Tensor] = None, count=None,
+                   height_threshold: Optional[float] = 1.3, resolution: float = 0.1, padding: float = 0.2,
+                   max_cells: int = 1 << 22) -> dict:
+    """The reference's top-down density grid (`create_density_grid_from_points`, `create_direct_floorplan`) of the
+    levelled cloud on the device (`dp_occupancy_grid`): the rows with y >= `height_threshold` (None or NaN: every
+    height) fall into cells of `resolution` metres over (x, z) from (min - padding).  Returns a dict of device
+    tensors: `density` (max_cells,) int32 holding the uint32 member counts, `height` (max_cells,) float32 (the
+    largest y of a cell, 0 where empty), `color` (max_cells, 3) uint8 or None (the colour of the highest member, the
+    smallest row among equals), `occupied` (max_cells,) uint8, `dims` int32 (H, W), `origin` float64 (min_x, min_z),
+    `stats` (8,) float64 in `GRID_STATS` order.  The first H * W entries are the grid, row-major, row 0 = smallest z;
+    x and z are as stored (no flip).  Asynchronous, no read-back.  stats["error"]: 1 without participants, 2 when
+    the grid would exceed `max_cells` (or 8192 cells on a side); dims are then (0, 0) and nothing is written."""
+    thr = float("nan") if height_threshold is None else float(height_threshold)
+    _check_floor(resolution, padding, thr, max_cells)
+    lib, pts, n, count, cptr, stream = _points_args(points, count, _FLOOR)
+    cols = None
+    if colors is not None:
+        cols = colors.contiguous()
+        if cols.dtype != torch.uint8 or tuple(cols.shape) != (n, 3):
+            raise ValueError("colors must be an (N, 3) uint8 tensor")
+    dev, mc = pts.device, int(max_cells)
+    ws = torch.empty(int(lib.dp_floorplan_workspace_size(mc, 0)), dtype=torch.uint8, device=dev)
+    out = {"density": torch.empty(mc, dtype=torch.int32, device=dev), "height": torch.empty(mc, dtype=torch.float32, device=dev),
+           "color": None if cols is None else torch.empty(mc, 3, dtype=torch.uint8, device=dev),
+           "occupied": torch.empty(mc, dtype=torch.uint8, device=dev), "dims": torch.empty(2, dtype=torch.int32, device=dev),
+           "origin": torch.empty(2, dtype=torch.float64, device=dev), "stats": torch.empty(8, dtype=torch.float64, device=dev)}
+    check(lib.dp_occupancy_grid(pts.data_ptr(), None if cols is None else cols.data_ptr(), cptr, n, thr, float(resolution),
+                                float(padding), mc, out["density"].data_ptr(), out["height"].data_ptr(),
+                                None if cols is None else out["color"].data_ptr(), out["occupied"].data_ptr(),
+                                out["dims"].data_ptr(), out["origin"].data_ptr(), out["stats"].data_ptr(), ws.data_ptr(),
+                                ws.numel(), stream), "dp_occupancy_grid")
+    return out
+
+
+def grid_morphology(grid: torch.Tensor, dims: torch.Tensor, close_size: int = 7, close_iters: int = 2, open_size: int = 3,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`cv2.morphologyEx` on a binary uint8 grid (`dp_grid_morphology`): `close_iters` closings by a `close_size`
+    square of ones, then one opening by `open_size` -- the reference's `process_height_slice` with the defaults.
+    OpenCV's border rule: a dilation reads outside cells as 0, an erosion as 1.  `grid` holds the capacity, `dims`
+    (device int32 H, W) says what is used.  Returns a 0 / 1 grid of the same capacity (`out=grid`: in place).
+    Asynchronous, no read-back."""
+    _check_floor(close_size=close_size, close_iters=close_iters, open_size=open_size)
+    lib, g, mc, stream = _grid_args(grid, dims)
+    if out is None:
+        out = torch.empty_like(g)
+    elif out.dtype != torch.uint8 or out.device != g.device or out.numel() != mc or not out.is_contiguous():
+        raise ValueError("out must be a contiguous uint8 tensor of the grid's size on its device")
+    ws = torch.empty(int(lib.dp_floorplan_workspace_size(mc, 0)), dtype=torch.uint8, device=g.device)
+    check(lib.dp_grid_morphology(g.data_ptr(), dims.data_ptr(), mc, int(close_size), int(close_iters), int(open_size),
+                                 out.data_ptr(), ws.data_ptr(), ws.numel(), stream), "dp_grid_morphology")
+    return out
+
+
+def grid_regions(grid: torch.Tensor, dims: torch.Tensor, density: torch.Tensor, height: torch.Tensor, origin: torch.Tensor,
+                 resolution: float = 0.1, max_regions: int = 4096):
+    """The 8-connected regions of a binary uint8 grid and their table (`dp_grid_regions`): (labels (max_cells,) int32 --
+    0 on background, regions numbered from 1 in row-major order of their first cell, as
+    `scipy.ndimage.label(structure=ones((3, 3)))` --, device int32 region count, table (max_regions,
+    len(REGION_COLUMNS)) float64 in `REGION_COLUMNS` order, stats (8,) float64 in `REGION_STATS` order).  `density`,
+    `height` and `origin` are `occupancy_grid`'s.  Regions past `max_regions` keep their labels, have no row and raise
+    stats["overflow"].  Asynchronous, no read-back."""
+    _check_floor(resolution, max_regions=max_regions)
+    lib, g, mc, stream = _grid_args(grid, dims)
+    dev, mr = g.device, int(max_regions)
+    for name, t, dt, numel in (("density", density, torch.int32, mc), ("height", height, torch.float32, mc),
+                               ("origin", origin, torch.float64, 2)):
+        if not torch.is_tensor(t) or t.device != dev or t.dtype != dt or t.numel() != numel or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of {numel} entries on the grid's device")
+    ws = torch.empty(int(lib.dp_floorplan_workspace_size(mc, mr)), dtype=torch.uint8, device=dev)
+    labels = torch.empty(mc, dtype=torch.int32, device=dev)
+    n_regions = torch.empty(1, dtype=torch.int32, device=dev)
+    table = torch.zeros(mr, len(REGION_COLUMNS), dtype=torch.float64, device=dev)
+    stats = torch.empty(8, dtype=torch.float64, device=dev)
+    check(lib.dp_grid_regions(g.data_ptr(), density.data_ptr(), height.data_ptr(), dims.data_ptr(), origin.data_ptr(), mc,
+                              float(resolution), mr, labels.data_ptr(), n_regions.data_ptr(), table.data_ptr(),
+                              stats.data_ptr(), ws.data_ptr(), ws.numel(), stream), "dp_grid_regions")
+    return labels, n_regions, table, stats
+
+
+def floorplan_image(labels: torch.Tensor, dims: torch.Tensor, table: torch.Tensor, n_regions: torch.Tensor,
+                    resolution: float = 0.1, min_area: float = 0.025, max_height: float = 2.5,
+                    color_by_height: bool = True) -> torch.Tensor:
+    """The picture of `create_direct_floorplan` from the regions (`dp_floorplan_image`): (max_cells, 3) uint8 RGB, the
+    first H * W pixels row-major with row 0 = smallest z.  White background; a region with area >= `min_area` is filled
+    with the reference's height colour of its mean height (grey 180 without `color_by_height`) and outlined in black
+    where its 4-neighbourhood leaves it; smaller regions are blank; the reference's 1 m scale bar where its condition
+    allows one, no text.  Asynchronous, no read-back."""
+    _check_floor(resolution, min_area=min_area, max_height=max_height)
+    lib, lab, mc, stream = _grid_args(labels, dims, torch.int32, "labels")
+    if table.device != lab.device or table.dtype != torch.float64 or table.dim() != 2 or \
+            table.shape[1] != len(REGION_COLUMNS) or not table.is_contiguous():
+        raise ValueError(f"table must be a contiguous (max_regions, {len(REGION_COLUMNS)}) float64 tensor on the labels' device")
+    if n_regions.device != lab.device or n_regions.dtype != torch.int32 or n_regions.numel() != 1:
+        raise ValueError("n_regions must be a device int32 scalar")
+    img = torch.empty(mc, 3, dtype=torch.uint8, device=lab.device)
+    check(lib.dp_floorplan_image(lab.data_ptr(), dims.data_ptr(), mc, table.data_ptr(), n_regions.data_ptr(),
+                                 int(table.shape[0]), float(resolution), float(min_area), float(max_height),
+                                 int(bool(color_by_height)), img.data_ptr(), stream), "dp_floorplan_image")
+    return img
+
+
+def floor_plan(points: torch.Tensor, colors: Optional[torch.Tensor] = None, count=None,
+               height_threshold: Optional[float] = 1.3, resolution: float = 0.1, padding: float = 0.2, close_size: int = 7,
+               close_iters: int = 2, open_size: int = 3, min_area: float = 0.025, max_height: float = 2.5,
+               max_cells: int = 1 << 22, max_regions: int = 4096) -> dict:
+    """The reference's occupancy floor plan (`cleaned_pointcloud_to_floorplan.py`) up to its contour tracing:
+    `occupancy_grid`, `grid_morphology`, `grid_regions`, `floorplan_image`, with the reference's height-threshold
+    values (resolution 0.05 doubled, padding 0.2, closing 7 x 7 twice, opening 3 x 3, min_area 0.1 / 4, height_max
+    2.5).  Returns `occupancy_grid`'s dict with `cleaned` (the grid after morphology), `labels`, `n_regions`, `table`,
+    `region_stats` and `image` added, and the parameters under `parameters`; all tensors on the device, nothing
+    synchronised.  Stated differences: a region's area is its cell count (the reference: `contourArea` of a traced
+    outline); no contour simplification, no polygons, no text."""
+    _check_floor(resolution, padding, float("nan") if height_threshold is None else float(height_threshold), max_cells,
+                 close_size, close_iters, open_size, min_area, max_height, max_regions)
+    out = occupancy_grid(points, colors, count, height_threshold, resolution, padding, max_cells)
+    out["cleaned"] = grid_morphology(out["occupied"], out["dims"], close_size, close_iters, open_size)
+    out["labels"], out["n_regions"], out["table"], out["region_stats"] = grid_regions(
+        out["cleaned"], out["dims"], out["density"], out["height"], out["origin"], resolution, max_regions)
+    out["image"] = floorplan_image(out["labels"], out["dims"], out["table"], out["n_regions"], resolution, min_area,
+                                   max_height)
+    out["parameters"] = {"height_threshold": None if height_threshold is None or height_threshold != height_threshold
+                         else float(height_threshold), "resolution": float(resolution), "padding": float(padding),
+                         "close_size": int(close_size), "close_iters": int(close_iters), "open_size": int(open_size),
+                         "min_area": float(min_area), "max_height": float(max_height)}
+    return out
+
+
+def floor_plan_summary(plan: dict) -> dict:
+    """The `{base}_floorplan.json` content and the picture from a `floor_plan` result: the one read-back (it
+    synchronises the current stream).  Returns {"origin", "resolution", "height", "width", "parameters", "stats",
+    "region_stats", "regions": one object per region with area >= min_area in label order, "image": (H, W, 3) uint8
+    numpy array}.  Everything but "image" is JSON-serialisable."""
+    small = torch.cat([plan["dims"].to(torch.float64), plan["origin"], plan["stats"], plan["region_stats"],
+                       plan["n_regions"].to(torch.float64)]).cpu().numpy()
+    h, w = int(small[0]), int(small[1])
+    params = plan["parameters"]
+    rows = min(int(small[20]), plan["table"].shape[0])
+    table = plan["table"][:rows].cpu().numpy()
+    img = plan["image"][:h * w].cpu().numpy().reshape(h, w, 3)
+    regions = [{"label": r + 1, **{k: (int(v) if k in ("cells", "gx0", "gz0", "gx1", "gz1", "points") else float(v))
+                                  for k, v in zip(REGION_COLUMNS, row)}}
+               for r, row in enumerate(table) if row[1] >= params["min_area"]]
+    return {"origin": [float(small[2]), float(small[3])], "resolution": params["resolution"], "height": h, "width": w,
+            "parameters": dict(params), "stats": {k: float(v) for k, v in zip(GRID_STATS, small[4:12])},
+            "region_stats": {k: float(v) for k, v in zip(REGION_STATS, small[12:20])}, "regions": regions, "image": img}
 
 
 GROUND_JSON = "ground.json"

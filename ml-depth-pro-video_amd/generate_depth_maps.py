@@ -259,15 +259,25 @@ def oriented_json_name(image_path: str) -> str:
     return f"{os.path.splitext(os.path.basename(image_path))[0]}_oriented.json"
 
 
+def floorplan_name(image_path: str) -> str:
+    """`{base}_floorplan.png` (--floor_plan); its origin, parameters, statistics and regions go to
+    `{base}_floorplan.json` beside it."""
+    return f"{os.path.splitext(os.path.basename(image_path))[0]}_floorplan.png"
+
+
+def floorplan_json_name(image_path: str) -> str:
+    return f"{os.path.splitext(os.path.basename(image_path))[0]}_floorplan.json"
+
+
 def plan_frames(image_paths, output_dir: str, world: int, rank: int, resume: bool, cleaned: bool = False,
-                clustered: bool = False, shaped: bool = False, oriented: bool = False) -> List[int]:
+                clustered: bool = False, shaped: bool = False, oriented: bool = False, floor: bool = False) -> List[int]:
     """Indices of the frames this rank processes: the frames still to do (all of them, or with
     `resume` those whose output file is missing -- decided by rank 0 alone and broadcast before
     any rank writes, so every rank shards the same list), dealt round-robin over the ranks.
     `cleaned` (--clean_pointcloud): a frame also counts as missing without its `{base}_clean.ply`;
     `clustered` (--cluster_pointcloud): and without its `{base}_clusters.json`; `shaped` (--fit_shapes): and
     without its `{base}_shapes.json`; `oriented` (--mesh_points): and without its `{base}_oriented.ply` or
-    `{base}_oriented.json`."""
+    `{base}_oriented.json`; `floor` (--floor_plan): and without its `{base}_floorplan.png` or `{base}_floorplan.json`."""
     todo = list(range(len(image_paths)))
     if resume:
         if rank == 0:
@@ -276,7 +286,9 @@ def plan_frames(image_paths, output_dir: str, world: int, rank: int, resume: boo
                 not clustered or os.path.exists(os.path.join(output_dir, clusters_name(image_paths[k])))) and (
                 not shaped or os.path.exists(os.path.join(output_dir, shapes_name(image_paths[k])))) and (
                 not oriented or (os.path.exists(os.path.join(output_dir, oriented_name(image_paths[k]))) and
-                                 os.path.exists(os.path.join(output_dir, oriented_json_name(image_paths[k])))))
+                                 os.path.exists(os.path.join(output_dir, oriented_json_name(image_paths[k]))))) and (
+                not floor or (os.path.exists(os.path.join(output_dir, floorplan_name(image_paths[k]))) and
+                              os.path.exists(os.path.join(output_dir, floorplan_json_name(image_paths[k])))))
             todo = [k for k in todo if not done(k)]
         if world > 1:
             box = [todo]
@@ -291,7 +303,8 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                               ground_percentile=5, rotation_offset=None, clean_pointcloud=False, stray_radius=0.1,
                               stray_neighbors=20, cluster_pointcloud=False, cluster_eps=0.2, cluster_min_samples=5,
                               cluster_height=1.3, cluster_max_points=100000, fit_shapes=False,
-                              circularity_threshold=0.85, mesh_points=False, voxel_size=0.05, normals_max_nn=30):
+                              circularity_threshold=0.85, mesh_points=False, voxel_size=0.05, normals_max_nn=30,
+                              floor_plan=False, floor_resolution=0.1, floor_height=1.3, floor_min_area=0.025):
     """Directory loop (reference :153-206), pipelined decode -> GPU -> encode, frame-sharded across ranks.
 
     Every rank writes its own frames' files; each frame has exactly one owner.  resume=True skips
@@ -326,6 +339,11 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
     normals over radius 2 * voxel_size and at most normals_max_nn neighbours, oriented towards the origin) on the
     same stream and writes `{base}_oriented.ply` (double x y z nx ny nz + uchar rgb) and `{base}_oriented.json`
     (parameters, point count, both statistics); without it the loop writes exactly what it wrote before.
+    floor_plan=True (implies clean_pointcloud) makes the reference's occupancy floor plan of the cleaned cloud
+    (`PC.floor_plan`: the rows with y >= floor_height -- NaN: every height -- rasterised at floor_resolution, closing
+    7 x 7 twice, opening 3 x 3, 8-connected regions, regions of at least floor_min_area m^2 drawn) on the same stream
+    and writes `{base}_floorplan.png` (RGB, row 0 = smallest z) and `{base}_floorplan.json` (origin, resolution, size,
+    parameters, statistics, one object per drawn region); without it the loop writes exactly what it wrote before.
     `model`: an already-built (model, transform) pair (tests); default: `_model`.
     Returns the number of frames this rank wrote.
     """
@@ -334,6 +352,11 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
     cluster = None
     shapes = None
     mesh = None
+    floor = None
+    if floor_plan:
+        check_floor(floor_resolution, floor_height, floor_min_area)
+        clean_pointcloud = True
+        floor = {"resolution": float(floor_resolution), "height_threshold": float(floor_height), "min_area": float(floor_min_area)}
     if mesh_points:
         check_mesh(voxel_size, normals_max_nn)
         clean_pointcloud = True
@@ -365,7 +388,8 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
     if ground is not None:
         ground["world"], ground["rank"] = world, rank
     mine = plan_frames(image_paths, output_dir, world, rank, resume, cleaned=clean is not None,
-                       clustered=cluster is not None, shaped=shapes is not None, oriented=mesh is not None)
+                       clustered=cluster is not None, shaped=shapes is not None, oriented=mesh is not None,
+                       floor=floor is not None)
     print(f"[rank {rank}/{world}] Found {len(image_paths)} images, processing {len(mine)}")
     if model is None:
         model = _model(_device(), half_precision)
@@ -423,7 +447,7 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                     gpu_img = True
                     if pointcloud:
                         pc = _points(depth, pred["focallength_px"], image, ground, image_paths[k], clean, cluster, shapes,
-                                     mesh)
+                                     mesh, floor)
                     ev = torch.cuda.Event()
                     ev.record()
                 else:
@@ -435,7 +459,9 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                             cnpy=os.path.join(output_dir, labels_name(image_paths[k])),
                             sjson=os.path.join(output_dir, shapes_name(image_paths[k])),
                             oply=os.path.join(output_dir, oriented_name(image_paths[k])),
-                            ojson=os.path.join(output_dir, oriented_json_name(image_paths[k]))):
+                            ojson=os.path.join(output_dir, oriented_json_name(image_paths[k])),
+                            fpng=os.path.join(output_dir, floorplan_name(image_paths[k])),
+                            fjson=os.path.join(output_dir, floorplan_json_name(image_paths[k]))):
                     if ev is not None:
                         ev.synchronize()
                     if status is not None:
@@ -448,6 +474,8 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                             _write_shapes(pc, cluster, shapes, sjson)
                         if mesh is not None:
                             _write_oriented(pc[-1], mesh, oply, ojson)
+                        if floor is not None:
+                            _write_floorplan(pc[-2] if mesh is not None else pc[-1], fpng, fjson)
                     if gpu_img:
                         _write_png(path, _host_image(host))
                         return path
@@ -504,6 +532,15 @@ def check_mesh(voxel_size, max_nn) -> None:
         raise ValueError(f"--normals_max_nn must be in [1, {PC.MAX_NN}] (got {max_nn})")
 
 
+def check_floor(resolution, height, min_area) -> None:
+    if not (np.isfinite(float(resolution)) and float(resolution) > 0):
+        raise ValueError(f"--floor_resolution must be finite and > 0 (got {resolution})")
+    if np.isinf(float(height)):
+        raise ValueError(f"--floor_height must be finite, or nan for every height (got {height})")
+    if not (np.isfinite(float(min_area)) and float(min_area) >= 0):
+        raise ValueError(f"--floor_min_area must be finite and >= 0 (got {min_area})")
+
+
 MAX_CLUSTERS = 4096     # rows of the per-frame cluster table (a frame with more lists the first 4096)
 
 
@@ -543,7 +580,7 @@ def _ground_plane(ground: dict, xyz, count, image_path):
 
 
 def _points(depth: torch.Tensor, f_px, image, ground=None, image_path=None, clean=None, cluster=None, shapes=None,
-            mesh=None):
+            mesh=None, floor=None):
     """Queue the frame's point cloud on the GPU (depth_to_3d, img_to_normalized_pointcloud.py:819-856),
     interleaved into PLY vertex records there, and their copy into a pinned host buffer, on the
     current stream, without a host synchronisation: the full-size record buffer + the point count
@@ -577,6 +614,12 @@ def _points(depth: torch.Tensor, f_px, image, ground=None, image_path=None, clea
         hbuf = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
         hbuf.copy_(t, non_blocking=True)
         out.append(hbuf)
+    if floor is not None:
+        # the occupancy floor plan of the cleaned cloud (--floor_plan): raster, morphology, regions and picture queued
+        # on the same stream.  Everything stays on the device (the grid's size is not known on the host yet); the
+        # writer makes the one read-back after the frame's event.
+        out.append(PC.floor_plan(xyz, cols, count, height_threshold=floor["height_threshold"], resolution=floor["resolution"],
+                                 min_area=floor["min_area"]))
     if mesh is not None:
         # the oriented point set of the cleaned cloud (--mesh_points): voxel grid, normals, orientation, and the PLY
         # records, queued on the same stream.  Only the voxel count and the statistics are copied here; the records
@@ -644,6 +687,25 @@ def _write_oriented(m: dict, mesh: dict, ply_path: str, json_path: str) -> None:
         json.dump(summary, f, indent=1)
 
 
+def _write_floorplan(plan: dict, png_path: str, json_path: str) -> None:
+    """Writer-thread side (after the frame's event, so the plan is complete): the one read-back on a stream of this
+    thread's own, then `{base}_floorplan.png` (PIL) and `{base}_floorplan.json`."""
+    import json
+
+    from PIL import Image
+
+    side = torch.cuda.Stream(plan["image"].device)
+    with torch.cuda.stream(side):
+        summary = PC.floor_plan_summary(plan)
+    img = summary.pop("image")
+    if img.size:
+        Image.fromarray(img, "RGB").save(png_path)
+    else:                                        # no participants, or a grid past the capacity: a 1 x 1 white picture
+        Image.new("RGB", (1, 1), (255, 255, 255)).save(png_path)
+    with open(json_path, "w") as f:
+        json.dump(summary, f, indent=1)
+
+
 def main():
     parser = argparse.ArgumentParser(description="Generate depth maps from input images")
     parser.add_argument("--input_dir", type=str, default="./TEMP/FRAMES", help="Directory containing input images")
@@ -696,10 +758,19 @@ def main():
                         help="Voxel edge of --mesh_points in metres (default 0.05); normals use radius 2 * voxel_size")
     parser.add_argument("--normals_max_nn", type=int, default=30,
                         help=f"Neighbours at the most per normal (1..{PC.MAX_NN}, default 30)")
+    parser.add_argument("--floor_plan", action="store_true",
+                        help="Write the occupancy floor plan of the cleaned cloud (implies --clean_pointcloud): top-down "
+                             "grid, closing and opening, connected regions; {frame}_floorplan.png and {frame}_floorplan.json")
+    parser.add_argument("--floor_resolution", type=float, default=0.1, help="Cell size of --floor_plan in metres (default 0.1)")
+    parser.add_argument("--floor_height", type=float, default=1.3,
+                        help="Rasterise the points with y >= this height in metres (default 1.3; nan: every height)")
+    parser.add_argument("--floor_min_area", type=float, default=0.025,
+                        help="Draw the regions of at least this area in square metres (default 0.025)")
     parser.add_argument("--resume", action="store_true",
                         help="Skip frames whose {frame}_depth.png (with --clean_pointcloud: and {frame}_clean.ply; with "
                              "--cluster_pointcloud: and {frame}_clusters.json; with --fit_shapes: and {frame}_shapes.json; with "
-                             "--mesh_points: and {frame}_oriented.ply / .json) already exists in --output_dir")
+                             "--mesh_points: and {frame}_oriented.ply / .json; with --floor_plan: and {frame}_floorplan.png / .json) "
+                             "already exists in --output_dir")
     parser.add_argument("--colormap", type=str, default="turbo",
                         choices=["turbo", "viridis", "plasma", "inferno", "magma", "cividis", "jet"],
                         help="Colormap for depth visualization")
@@ -714,6 +785,8 @@ def main():
         check_circularity(args.circularity_threshold)
         if args.mesh_points:
             check_mesh(args.voxel_size, args.normals_max_nn)
+        if args.floor_plan:
+            check_floor(args.floor_resolution, args.floor_height, args.floor_min_area)
     except ValueError as e:
         parser.error(str(e))
     batch_generate_depth_maps(input_dir=args.input_dir, output_dir=args.output_dir, pattern=args.pattern,
@@ -728,7 +801,9 @@ def main():
                               cluster_eps=args.cluster_eps, cluster_min_samples=args.cluster_min_samples,
                               cluster_height=args.cluster_height, cluster_max_points=args.cluster_max_points,
                               fit_shapes=args.fit_shapes, circularity_threshold=args.circularity_threshold,
-                              mesh_points=args.mesh_points, voxel_size=args.voxel_size, normals_max_nn=args.normals_max_nn)
+                              mesh_points=args.mesh_points, voxel_size=args.voxel_size, normals_max_nn=args.normals_max_nn,
+                              floor_plan=args.floor_plan, floor_resolution=args.floor_resolution,
+                              floor_height=args.floor_height, floor_min_area=args.floor_min_area)
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()

@@ -46,6 +46,8 @@ def main():
                     help="fit the clusters' shapes (--fit_shapes of the loop; implies --cluster-pointcloud)")
     ap.add_argument("--mesh-points", action="store_true",
                     help="write the oriented mesh points (--mesh_points of the loop; implies --clean-pointcloud)")
+    ap.add_argument("--floor-plan", action="store_true",
+                    help="write the occupancy floor plan (--floor_plan of the loop; implies --clean-pointcloud)")
     ap.add_argument("--raw", action="store_true")
     ap.add_argument("--workers", type=int, default=None,
                     help="decode and encode threads each (default: the loop's own defaults)")
@@ -134,7 +136,7 @@ def main():
     t_setup = time.time() - t
     if args.fit_shapes:
         args.cluster_pointcloud = True
-    if args.cluster_pointcloud or args.mesh_points:
+    if args.cluster_pointcloud or args.mesh_points or args.floor_plan:
         args.clean_pointcloud = True
     if args.clean_pointcloud:
         args.normalize_ground = True
@@ -151,6 +153,8 @@ def main():
         kw["fit_shapes"] = True
     if args.mesh_points:
         kw["mesh_points"] = True
+    if args.floor_plan:
+        kw["floor_plan"] = True
     if args.workers:
         kw.update(decode_workers=args.workers, encode_workers=args.workers)
     import inspect
@@ -237,7 +241,7 @@ def main():
         "what": "generate_depth_maps.batch_generate_depth_maps end to end, 1 GPU",
         "frames": args.frames, "size": [W, H], "pointcloud": args.pointcloud, "normalize_ground": args.normalize_ground,
         "clean_pointcloud": args.clean_pointcloud, "cluster_pointcloud": args.cluster_pointcloud,
-        "fit_shapes": args.fit_shapes, "mesh_points": args.mesh_points,
+        "fit_shapes": args.fit_shapes, "mesh_points": args.mesh_points, "floor_plan": args.floor_plan,
         "raw": args.raw,
         "ply_records": "host (numpy)" if args.ply_host else "GPU",
         "png_writer": "bytes copies" if args.png_copy else "zero-copy parts",

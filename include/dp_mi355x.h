@@ -1068,6 +1068,67 @@ int dp_floorplan_image(const int32_t* labels, const int32_t* dims, int32_t max_c
                        const int32_t* n_regions_dev, int32_t max_regions, double resolution, double min_area,
                        double max_height, int32_t color_by_height, uint8_t* image_out, dp_stream_t stream);
 
+/* ---- Scale-invariant boundary metric (additive to ABI 20, csrc/dp_boundary.hip) ---------------------
+ *
+ * The edge counts behind SI_boundary_F1 and SI_boundary_Recall of the reference's
+ * depth_pro/eval/boundary_metrics.py, and the edge maps themselves.  The counts are integers, so they
+ * equal the reference's exactly; the scores are made from them on the host (depth_pro/eval).  fp32 with
+ * IEEE division and denormals (no fast-math), no host synchronisation, no allocation, argument errors
+ * returned as DP_ERR_* before any launch.
+ *
+ *   1. Input: pred is a float32 H x W depth with a row stride of ld_pred elements.  The target is a
+ *      float32 depth (DP_BOUNDARY_DEPTH, the F1 case) or a uint8 0 / non-zero mask (DP_BOUNDARY_MASK, the
+ *      recall case), ld_target in elements of its own type.
+ *   2. Inverse depth: inv = 1.0f / (d < 1e-6f ? 1e-6f : d).  A NaN depth stays NaN (numpy's clip), +inf
+ *      gives 0; -inf, 0 and negatives give 1e6.  With DP_BOUNDARY_INVERSE ORed into target_kind, pred and
+ *      a depth target are inverse depths already and are used as they are (the reference's boundary_f1 and
+ *      edge_recall_matting take those).
+ *   3. Ratios, in the reference's return order (left, top, right, bottom): left = inv[y,x] / inv[y,x+1] and
+ *      right = inv[y,x+1] / inv[y,x], both H x (W-1); top = inv[y,x] / inv[y+1,x] and bottom =
+ *      inv[y+1,x] / inv[y,x], both (H-1) x W.  fp32 divisions: x / 0 is inf (an edge), 0 / 0 and anything
+ *      with a NaN is no edge.
+ *   4. Plain edge (fgbg_depth): (double)ratio > t, t a double.  The kernels compare ratio > f in fp32 with
+ *      f the largest float32 <= t, which is the same predicate for every float32 ratio (dp_boundary.hip).
+ *   5. Thinned edge (fgbg_depth_thinned): within each row of a horizontal map, of every maximal run of
+ *      consecutive cells with ratio > t one cell stays, the first of the largest values; within each column
+ *      of a vertical map the same, going down, the topmost of equal maxima.  Runs do not continue from one
+ *      line into the next, a NaN ends a run, and of two infs in a run the first stays.
+ *   6. Mask edges (fgbg_binary_mask) of a 0 / 1 mask m: left = m[y,x] & ~m[y,x+1], right = m[y,x+1] & ~m[y,x],
+ *      top = m[y,x] & ~m[y+1,x], bottom = m[y+1,x] & ~m[y,x].
+ *   7. counts[k][dir][0..2] = cells that are an edge of both images, of the target, of the prediction, for
+ *      threshold k and direction dir.  DP_BOUNDARY_DEPTH: plain edges of both.  DP_BOUNDARY_MASK: thinned
+ *      edges of the prediction, mask edges of the target (the same number for every k).
+ *   8. The reference's edge_recall_matting compares ratio > np.float32(t) (a weak Python scalar), its
+ *      boundary_f1 (double)ratio > t (an np.float64 scalar).  This library always does the second: the
+ *      recall's caller passes (double)(float)t.
+ *
+ * dp_boundary_counts: all n_t thresholds (host array) in one call; counts (device, n_t * 12 uint64) is written
+ *   whole.  dp_boundary_edges: maps = 4 planes of H * W bytes in the order of 3., map cell (y, x) at y * W + x,
+ *   0 / 1, 0 outside each map's extent (the last column of left / right, the last row of top / bottom); plain
+ *   edges, or thinned ones with thinned != 0.
+ *   H, W in [1, DP_BOUNDARY_MAX_DIM] (1 x 1: every count is 0), n_t in [1, DP_BOUNDARY_MAX_T], ld >= W (else
+ *   DP_ERR_SHAPE).  A null pointer, a threshold that is not finite, a target_kind other than the two kinds with
+ *   or without the flag, a workspace below dp_boundary_workspace_size(H, W, n_t) (edges: n_t = 1) or not 4-byte
+ *   aligned, counts not 8-byte aligned: DP_ERR_ARG.  The thinned passes cut every line into segments of
+ *   DP_BOUNDARY_SEGMENT cells; the workspace holds two runs per segment, threshold and direction.
+ */
+#define DP_BOUNDARY_MAX_DIM 16384
+#define DP_BOUNDARY_MAX_T   32
+#define DP_BOUNDARY_DIRS    4     /* left, top, right, bottom */
+#define DP_BOUNDARY_COUNTS  3     /* both, target, predicted */
+#define DP_BOUNDARY_DEPTH   0     /* target: float32 depth, plain edges on both sides */
+#define DP_BOUNDARY_MASK    1     /* target: uint8 0/1, prediction thinned */
+#define DP_BOUNDARY_INVERSE 2     /* flag: the depths are inverse depths already */
+#define DP_BOUNDARY_SEGMENT 64
+int64_t dp_boundary_workspace_size(int32_t H, int32_t W, int32_t n_t);
+int dp_boundary_counts(const float* pred, int64_t ld_pred, const void* target, int64_t ld_target, int32_t target_kind,
+                       int32_t H, int32_t W, const double* thresholds /* host */, int32_t n_t,
+                       uint64_t* counts /* device, [n_t][4][3], written whole */, void* ws, int64_t ws_bytes,
+                       dp_stream_t stream);
+int dp_boundary_edges(const float* depth, int64_t ld, int32_t H, int32_t W, double t, int32_t thinned,
+                      uint8_t* maps /* device, 4 planes of H*W bytes, 0 outside each map's extent */, void* ws,
+                      int64_t ws_bytes, dp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

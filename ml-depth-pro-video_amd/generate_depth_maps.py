@@ -269,15 +269,26 @@ def floorplan_json_name(image_path: str) -> str:
     return f"{os.path.splitext(os.path.basename(image_path))[0]}_floorplan.json"
 
 
+def boundary_name(image_path: str) -> str:
+    """`{base}_boundary.json` (--boundary_dir): the frame's boundary score against `{base}.npy` of that directory."""
+    return f"{os.path.splitext(os.path.basename(image_path))[0]}_boundary.json"
+
+
+def boundary_target_path(image_path: str, boundary_dir: str) -> str:
+    return os.path.join(boundary_dir, f"{os.path.splitext(os.path.basename(image_path))[0]}.npy")
+
+
 def plan_frames(image_paths, output_dir: str, world: int, rank: int, resume: bool, cleaned: bool = False,
-                clustered: bool = False, shaped: bool = False, oriented: bool = False, floor: bool = False) -> List[int]:
+                clustered: bool = False, shaped: bool = False, oriented: bool = False, floor: bool = False,
+                boundary: Optional[str] = None) -> List[int]:
     """Indices of the frames this rank processes: the frames still to do (all of them, or with
     `resume` those whose output file is missing -- decided by rank 0 alone and broadcast before
     any rank writes, so every rank shards the same list), dealt round-robin over the ranks.
     `cleaned` (--clean_pointcloud): a frame also counts as missing without its `{base}_clean.ply`;
     `clustered` (--cluster_pointcloud): and without its `{base}_clusters.json`; `shaped` (--fit_shapes): and
     without its `{base}_shapes.json`; `oriented` (--mesh_points): and without its `{base}_oriented.ply` or
-    `{base}_oriented.json`; `floor` (--floor_plan): and without its `{base}_floorplan.png` or `{base}_floorplan.json`."""
+    `{base}_oriented.json`; `floor` (--floor_plan): and without its `{base}_floorplan.png` or `{base}_floorplan.json`;
+    `boundary` (--boundary_dir): a frame with a target `{base}.npy` in that directory, and without its `{base}_boundary.json`."""
     todo = list(range(len(image_paths)))
     if resume:
         if rank == 0:
@@ -288,7 +299,9 @@ def plan_frames(image_paths, output_dir: str, world: int, rank: int, resume: boo
                 not oriented or (os.path.exists(os.path.join(output_dir, oriented_name(image_paths[k]))) and
                                  os.path.exists(os.path.join(output_dir, oriented_json_name(image_paths[k]))))) and (
                 not floor or (os.path.exists(os.path.join(output_dir, floorplan_name(image_paths[k]))) and
-                              os.path.exists(os.path.join(output_dir, floorplan_json_name(image_paths[k])))))
+                              os.path.exists(os.path.join(output_dir, floorplan_json_name(image_paths[k]))))) and (
+                not boundary or not os.path.exists(boundary_target_path(image_paths[k], boundary)) or
+                os.path.exists(os.path.join(output_dir, boundary_name(image_paths[k]))))
             todo = [k for k in todo if not done(k)]
         if world > 1:
             box = [todo]
@@ -304,7 +317,8 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                               stray_neighbors=20, cluster_pointcloud=False, cluster_eps=0.2, cluster_min_samples=5,
                               cluster_height=1.3, cluster_max_points=100000, fit_shapes=False,
                               circularity_threshold=0.85, mesh_points=False, voxel_size=0.05, normals_max_nn=30,
-                              floor_plan=False, floor_resolution=0.1, floor_height=1.3, floor_min_area=0.025):
+                              floor_plan=False, floor_resolution=0.1, floor_height=1.3, floor_min_area=0.025,
+                              boundary_dir=None):
     """Directory loop (reference :153-206), pipelined decode -> GPU -> encode, frame-sharded across ranks.
 
     Every rank writes its own frames' files; each frame has exactly one owner.  resume=True skips
@@ -344,6 +358,11 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
     7 x 7 twice, opening 3 x 3, 8-connected regions, regions of at least floor_min_area m^2 drawn) on the same stream
     and writes `{base}_floorplan.png` (RGB, row 0 = smallest z) and `{base}_floorplan.json` (origin, resolution, size,
     parameters, statistics, one object per drawn region); without it the loop writes exactly what it wrote before.
+    boundary_dir=DIR scores each frame whose target `DIR/{base}.npy` exists and has the depth's shape with the Depth Pro
+    boundary metric (`depth_pro.eval.boundary_metrics`), from the device depth before its read-back, on the same stream:
+    a float32 target is a depth (SI_boundary_F1), a bool or uint8 one a mask (SI_boundary_Recall, the raw values
+    thresholded by > 0.1).  `{base}_boundary.json` holds the kind, the score, the per-threshold counts, the thresholds,
+    H and W; a missing or unusable target is reported and the frame goes on without a score; rank 0 prints the mean.
     `model`: an already-built (model, transform) pair (tests); default: `_model`.
     Returns the number of frames this rank wrote.
     """
@@ -353,6 +372,9 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
     shapes = None
     mesh = None
     floor = None
+    if boundary_dir is not None:
+        check_boundary_dir(boundary_dir)
+    scores = []
     if floor_plan:
         check_floor(floor_resolution, floor_height, floor_min_area)
         clean_pointcloud = True
@@ -389,7 +411,7 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
         ground["world"], ground["rank"] = world, rank
     mine = plan_frames(image_paths, output_dir, world, rank, resume, cleaned=clean is not None,
                        clustered=cluster is not None, shaped=shapes is not None, oriented=mesh is not None,
-                       floor=floor is not None)
+                       floor=floor is not None, boundary=boundary_dir)
     print(f"[rank {rank}/{world}] Found {len(image_paths)} images, processing {len(mine)}")
     if model is None:
         model = _model(_device(), half_precision)
@@ -439,6 +461,7 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                 if status is not None and hasattr(status, "claim"):
                     status.claim()
                 pc = None
+                bd = None
                 gpu_img = False
                 if depth.is_cuda:
                     # the PNG content (colour / raw) made on the GPU, and every device->host copy,
@@ -448,6 +471,8 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                     if pointcloud:
                         pc = _points(depth, pred["focallength_px"], image, ground, image_paths[k], clean, cluster, shapes,
                                      mesh, floor)
+                    if boundary_dir is not None:
+                        bd = _boundary(depth, boundary_target_path(image_paths[k], boundary_dir))
                     ev = torch.cuda.Event()
                     ev.record()
                 else:
@@ -461,7 +486,8 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                             oply=os.path.join(output_dir, oriented_name(image_paths[k])),
                             ojson=os.path.join(output_dir, oriented_json_name(image_paths[k])),
                             fpng=os.path.join(output_dir, floorplan_name(image_paths[k])),
-                            fjson=os.path.join(output_dir, floorplan_json_name(image_paths[k]))):
+                            fjson=os.path.join(output_dir, floorplan_json_name(image_paths[k])), bd=bd,
+                            bjson=os.path.join(output_dir, boundary_name(image_paths[k]))):
                     if ev is not None:
                         ev.synchronize()
                     if status is not None:
@@ -476,6 +502,8 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                             _write_oriented(pc[-1], mesh, oply, ojson)
                         if floor is not None:
                             _write_floorplan(pc[-2] if mesh is not None else pc[-1], fpng, fjson)
+                    if bd is not None:
+                        scores.append(_write_boundary(bd, bjson))
                     if gpu_img:
                         _write_png(path, _host_image(host))
                         return path
@@ -490,6 +518,8 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
             collect(f)
     if ground is not None and world > 1 and not ground["resolved"]:
         _ground_plane(ground, None, None, None)      # a rank without frames still takes part in the broadcast
+    if boundary_dir is not None:
+        _report_boundary(scores, world, rank)
     dt = time.time() - t0
     print(f"Processing complete: {successful}/{len(mine)} images successfully processed "
           f"({len(mine) / max(dt, 1e-9):.2f} frames/s on rank {rank})")
@@ -539,6 +569,11 @@ def check_floor(resolution, height, min_area) -> None:
         raise ValueError(f"--floor_height must be finite, or nan for every height (got {height})")
     if not (np.isfinite(float(min_area)) and float(min_area) >= 0):
         raise ValueError(f"--floor_min_area must be finite and >= 0 (got {min_area})")
+
+
+def check_boundary_dir(boundary_dir) -> None:
+    if not os.path.isdir(str(boundary_dir)):
+        raise ValueError(f"--boundary_dir must be an existing directory (got {boundary_dir})")
 
 
 MAX_CLUSTERS = 4096     # rows of the per-frame cluster table (a frame with more lists the first 4096)
@@ -687,6 +722,63 @@ def _write_oriented(m: dict, mesh: dict, ply_path: str, json_path: str) -> None:
         json.dump(summary, f, indent=1)
 
 
+def _boundary(depth: torch.Tensor, target_path: str):
+    """Queue the frame's boundary counts against its target on the current stream (depth_pro.eval.boundary_metrics:
+    the depth is still on the device) and their copy into pinned host memory.  None, with a line of report, when the
+    target is missing or cannot be used."""
+    from depth_pro.eval import boundary_metrics as BM
+
+    if not os.path.exists(target_path):
+        print(f"No boundary target {target_path}: frame not scored")
+        return None
+    try:
+        target = np.load(target_path)
+        if tuple(target.shape) != tuple(depth.shape):
+            raise ValueError(f"shape {target.shape}, the depth has {tuple(depth.shape)}")
+        if target.dtype == np.float32:
+            kind, name = BM.DP_BOUNDARY_DEPTH, "depth"
+        elif target.dtype in (np.bool_, np.uint8):
+            kind, name = BM.DP_BOUNDARY_MASK, "mask"
+            target = target > 0.1                                           # the reference's alpha_threshold on the raw values
+        else:
+            raise ValueError(f"dtype {target.dtype} (float32: depth; bool / uint8: mask)")
+        thresholds, _ = BM.get_thresholds_and_weights(1.05, 1.25, 10)
+        passed = thresholds if kind == BM.DP_BOUNDARY_DEPTH else thresholds.astype(np.float32).astype(np.float64)
+        counts = BM.boundary_counts(depth, target, passed, kind).view(torch.int64)
+    except Exception as e:
+        print(f"Boundary target {target_path} not used: {e}")
+        return None
+    host = torch.empty(counts.shape, dtype=counts.dtype, pin_memory=True)
+    host.copy_(counts, non_blocking=True)
+    return {"kind": kind, "name": name, "counts": host, "thresholds": thresholds, "shape": tuple(depth.shape)}
+
+
+def _write_boundary(bd: dict, json_path: str) -> float:
+    """Writer-thread side (after the frame's event): the score from the counts, `{base}_boundary.json`."""
+    import json
+
+    from depth_pro.eval import boundary_metrics as BM
+
+    counts = bd["counts"].numpy().tolist()
+    score = float(BM.weighted_score(counts, bd["thresholds"], bd["kind"]))
+    with open(json_path, "w") as f:
+        json.dump({"kind": bd["name"], "metric": "SI_boundary_F1" if bd["kind"] == BM.DP_BOUNDARY_DEPTH else "SI_boundary_Recall",
+                   "score": score, "thresholds": [float(t) for t in bd["thresholds"]], "directions": list(BM.DIRECTIONS),
+                   "count_names": list(BM.COUNTS), "counts": counts, "H": bd["shape"][0], "W": bd["shape"][1]}, f, indent=1)
+    return score
+
+
+def _report_boundary(scores, world: int, rank: int) -> None:
+    """Rank 0 prints the mean boundary score over the frames scored (one all-reduce of sum and count with several ranks)."""
+    total, n = float(sum(scores)), len(scores)
+    if world > 1:
+        box = torch.tensor([total, float(n)], dtype=torch.float64, device=_device() if dist.get_backend() == "nccl" else "cpu")
+        dist.all_reduce(box)
+        total, n = float(box[0]), int(box[1])
+    if rank == 0:
+        print(f"mean boundary score over {n} frames: {total / n:.6f}" if n else "no frame had a usable boundary target")
+
+
 def _write_floorplan(plan: dict, png_path: str, json_path: str) -> None:
     """Writer-thread side (after the frame's event, so the plan is complete): the one read-back on a stream of this
     thread's own, then `{base}_floorplan.png` (PIL) and `{base}_floorplan.json`."""
@@ -766,11 +858,14 @@ def main():
                         help="Rasterise the points with y >= this height in metres (default 1.3; nan: every height)")
     parser.add_argument("--floor_min_area", type=float, default=0.025,
                         help="Draw the regions of at least this area in square metres (default 0.025)")
+    parser.add_argument("--boundary_dir", type=str, default=None,
+                        help="Score each frame against DIR/{frame}.npy with the Depth Pro boundary metric (float32: a depth, "
+                             "SI_boundary_F1; bool / uint8: a mask, SI_boundary_Recall); writes {frame}_boundary.json")
     parser.add_argument("--resume", action="store_true",
                         help="Skip frames whose {frame}_depth.png (with --clean_pointcloud: and {frame}_clean.ply; with "
                              "--cluster_pointcloud: and {frame}_clusters.json; with --fit_shapes: and {frame}_shapes.json; with "
-                             "--mesh_points: and {frame}_oriented.ply / .json; with --floor_plan: and {frame}_floorplan.png / .json) "
-                             "already exists in --output_dir")
+                             "--mesh_points: and {frame}_oriented.ply / .json; with --floor_plan: and {frame}_floorplan.png / .json; with "
+                             "--boundary_dir, for a frame with a target: and {frame}_boundary.json) already exists in --output_dir")
     parser.add_argument("--colormap", type=str, default="turbo",
                         choices=["turbo", "viridis", "plasma", "inferno", "magma", "cividis", "jet"],
                         help="Colormap for depth visualization")
@@ -787,6 +882,8 @@ def main():
             check_mesh(args.voxel_size, args.normals_max_nn)
         if args.floor_plan:
             check_floor(args.floor_resolution, args.floor_height, args.floor_min_area)
+        if args.boundary_dir is not None:
+            check_boundary_dir(args.boundary_dir)
     except ValueError as e:
         parser.error(str(e))
     batch_generate_depth_maps(input_dir=args.input_dir, output_dir=args.output_dir, pattern=args.pattern,
@@ -803,7 +900,8 @@ def main():
                               fit_shapes=args.fit_shapes, circularity_threshold=args.circularity_threshold,
                               mesh_points=args.mesh_points, voxel_size=args.voxel_size, normals_max_nn=args.normals_max_nn,
                               floor_plan=args.floor_plan, floor_resolution=args.floor_resolution,
-                              floor_height=args.floor_height, floor_min_area=args.floor_min_area)
+                              floor_height=args.floor_height, floor_min_area=args.floor_min_area,
+                              boundary_dir=args.boundary_dir)
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()

@@ -851,8 +851,8 @@ int dp_cluster_table(const double* points, const int32_t* labels, const int32_t*
  *     is not down to one chunk by then (its hull has more vertices, or shrinks too slowly) gets error
  *     flag 1, kind 0, an empty hull range and every other column but the count 0: nothing is fitted
  *     from a truncated hull.  Other clusters of the call are not affected.
- * Out of scope: detect_and_split_l_shapes (:79-282), a chain of OpenCV morphology and
- * connected-components calls on a per-rectangle grid; its input is the rectangle list produced here.
+ * The last step of fit_shapes_to_clusters, detect_and_split_l_shapes (:79-282), works on the rectangle
+ * list produced here: "L-shape split" (additive to ABI 20) below.
  * circularity_threshold NaN, max_clusters < 0 or n_max < 0: DP_ERR_SHAPE.
  */
 #define DP_SHAPES_H_MAX 2048
@@ -1034,7 +1034,7 @@ int dp_estimate_normals(const double* points, const int32_t* n_dev, int32_t n_ma
  *   halving keeps short but which is not bounded below the region's size.
  *   Stated difference: the reference measures a region by cv2.contourArea of its traced outline and
  *   drops those of 5 or less; here the area is the cell count.  findContours, approxPolyDP, the polygons
- *   file and detect_and_split_l_shapes are not built.
+ *   file are not built (detect_and_split_l_shapes belongs to the shapes stage: "L-shape split" below).
  *
  * Picture (dp_floorplan_image): image_out uint8 [max_cells][3], RGB, H x W as the grids (row 0 = smallest z).
  *  12. White background.  A cell whose label has a table row with area >= min_area is filled; the cells
@@ -1067,6 +1067,107 @@ int dp_grid_regions(const uint8_t* grid, const uint32_t* density, const float* h
 int dp_floorplan_image(const int32_t* labels, const int32_t* dims, int32_t max_cells, const double* table,
                        const int32_t* n_regions_dev, int32_t max_regions, double resolution, double min_area,
                        double max_height, int32_t color_by_height, uint8_t* image_out, dp_stream_t stream);
+
+/*
+ * ---- L-shape split (additive to ABI 20, csrc/dp_lshape.hip) -----------------------------------------
+ * The end of the reference's fit_shapes_to_clusters: the rectangle list it builds from the cluster
+ * shapes (the forced halving of a very large rectangle, split_large_rectangle :284-330, :387-396) and
+ * `rectangles = detect_and_split_l_shapes(rectangles, points_2d)` (simple_pointcloud_viewer.py:79-282,
+ * :410), which replaces a large rectangle that holds separate occupied parts by one rectangle per part.
+ * The point-cloud sections' conventions hold: fp64 points [n_max][3], n_dev a device int32 (NULL: n_max;
+ * clamped to [0, n_max]), n_max = 0, *n_dev = 0 and zero rectangles valid, everything on the caller's
+ * stream with no synchronisation and no host read-back, each fp64 product, sum and difference rounded on
+ * its own (no FMA), argument errors returned as DP_ERR_* before any launch.  sin and cos are the device's.
+ * The block is additive: no existing entry point or layout changes, and DP_ABI_VERSION stays 20.
+ * A rectangle row is fp64 [8]: centre u, centre v, width, height, angle in degrees, cluster, flags, 0,
+ * in the frame u = -x, v = z of "Cluster shapes".  flags: 1 = a half of a forced split, + 2 = a part of an
+ * L-shape split.
+ *
+ * Rectangle list (dp_shape_rectangles).  Reads shapes, the [max_clusters][16] table of dp_cluster_shapes,
+ * rows c < K = min(*n_clusters_dev, max_clusters).  Each kind == 1 row, in cluster order, becomes one
+ * rectangle (centre, width, height, angle of its columns 2..6, flags 0).  A row with width * height > 100
+ * and count > 1000 becomes two, flags 1, with a = angle * pi / 180:
+ *   width > height: d = width / 4:  (cu - d*cos a, cv - d*sin a, width / 2, height, angle), then
+ *                                   (cu + d*cos a, cv + d*sin a, width / 2, height, angle);
+ *   otherwise:      d = height / 4: (cu - d*sin a, cv + d*cos a, width, height / 2, angle), then
+ *                                   (cu + d*sin a, cv - d*cos a, width, height / 2, angle).
+ *   rects_out    fp64 [2 * max_clusters][8], the rows below *n_rects_dev written
+ *   n_rects_dev  device int32: the number of rectangles
+ *
+ * Split (dp_lshape_split).  Input: the points, labels int32 [n_max] as dp_cluster_dbscan wrote them, a
+ * rectangle list rects [max_rects][8] with its device count (clamped to [0, max_rects]).  The points that
+ * take part are the reference's points_2d: the live rows with label >= -1 -- every DBSCAN participant,
+ * noise and the members of other clusters included, not the rectangle's own cluster alone -- at u = -x,
+ * v = z.  For each rectangle r = (cu, cv, w, h, angle, ...) of the list, in list order, with the
+ * reference's constants:
+ *   1. w * h < 10: kept (status 1).
+ *   2. a = -angle * pi / 180, c = cos a, s = sin a.  A point is at x' = du*c - dv*s, y' = du*s + dv*c with
+ *      du = u - cu, dv = v - cv (the reference's np.dot(centered, R.T)), and inside iff -w/2 < x' < w/2
+ *      and -h/2 < y' < h/2: strict, as Polygon.contains is.
+ *      Stated difference: the reference tests against cv2.boxPoints corners rounded to float32; this
+ *      tests in the rectangle's own frame in fp64.
+ *   3. Fewer than 50 points inside: kept (status 2).
+ *   4. gw = (int)(w / 0.2) + 1, gh = (int)(h / 0.2) + 1 (saturated at 2^31 - 1).  gw <= 2 or gh <= 2: kept
+ *      (status 3).  A side above DP_LSHAPE_MAX_SIDE: kept, error flag 1 (status 9).  Grids take their
+ *      gw * gh cells from the capacity max_cells in list order, for every rectangle that passed rule 1 and
+ *      the two side tests (whatever rule 3 says of it): once the grids up to and including r need more
+ *      than max_cells, r and every later such rectangle is kept with error flag 1 (status 9).  Nothing is
+ *      split from a truncated grid.
+ *   5. An inside point sets cell gx = (int)((x' + w/2) / 0.2), gy = (int)((y' + h/2) / 0.2) when
+ *      0 <= gx < gw and 0 <= gy < gh.  b = the set cells.
+ *   6. Dilation by 2 x 2 ones with OpenCV's default anchor (1, 1):
+ *      d[y][x] = b[y][x] | b[y][x-1] | b[y-1][x] | b[y-1][x-1], cells outside the grid reading 0.
+ *   7. empty = !d.  Its 4-connected components with at least 6 cells form empty_mask.  None: kept
+ *      (status 4).  ratio = (cells of empty_mask) / (gw * gh), one fp64 division; ratio < 0.2 or
+ *      ratio > 0.6: kept (status 5).
+ *   8. occupied = !empty_mask (smaller holes count as occupied, as in the reference).  Fewer than 2
+ *      4-connected components of it: kept (status 6).
+ *   9. Each occupied component with at least 6 cells, in row-major order of its first cell
+ *      (scipy.ndimage.label's numbering; cv2.connectedComponents' own is not documented, and it only
+ *      fixes the order of the output rows): its points are (x * 0.2 - w/2, y * 0.2 - h/2) over its cells;
+ *      (sx, sy), sub_w, sub_h, sub_angle = their minimum-area rectangle by rules 2 and 3 of "Cluster
+ *      shapes" (hull, calipers, ties to the smallest edge, angle folded into [0, 90)).
+ *      Stated difference: cv2.minAreaRect works on float32 points with its own angle convention.
+ *      The centre goes back as the reference writes it: ocx = (sx*c - sy*s) + cu, ocy = (sx*s + sy*c) + cv
+ *      with the c and s of rule 2 -- np.dot(centre, rotation_matrix.T), the reference's
+ *      rotation_matrix_inv taken literally, which turns by -angle a second time instead of turning back.
+ *      angle' = fmod(sub_angle + angle, 180).  The part is listed iff sub_w * sub_h > 1.0.
+ *  10. With L parts listed and S = the sum of their sub_w * sub_h in listed order: L < 2: kept (status 7);
+ *      not 0.4 < S / (w * h) < 1.3: kept (status 8); otherwise the parts replace r (status 0), each
+ *      (ocx, ocy, sub_w, sub_h, angle', r's cluster, r's flags + 2, 0).
+ *   The reference's "largest empty region" loop (:201-208) computes a value nothing reads; it is left out.
+ *   rects_out  fp64 [max_out][8]: the list in order, a replaced rectangle's parts in its place; a kept
+ *              rectangle's row is copied as it came.  Offsets from a device scan of the per-rectangle counts.
+ *   n_out_dev  device int32 [2]: rows written = min(rows, max_out); error word: 1 when rows > max_out (the
+ *              rows past max_out are dropped), else 0.
+ *   info_out   fp64 [max_rects][8], row r: status, points inside (0 under status 1), gw, gh (0 under
+ *              status 1), cells of empty_mask (0 under status 1, 2, 3, 9), occupied components (0 under
+ *              those and 4, 5), parts listed (0 unless status 0, 7, 8), error flag.
+ *   workspace  >= dp_lshape_workspace_size(max_rects, max_cells) bytes of device memory, 8-byte aligned,
+ *              owned by the call until the stream has passed it (content need not be initialised).  About
+ *              29 bytes per cell and 130 per rectangle.
+ *   n_max, max_rects, max_out or max_cells < 0: DP_ERR_SHAPE.
+ *
+ * Method.  One workgroup lists the candidates (rule 1) and scans the grid sizes into cell offsets: all
+ * grids are ranges of one byte-per-cell array.  One pass over points x candidates: a workgroup keeps 64
+ * candidates in LDS, rejects by the bounding circle before the rotation, counts the inside points by
+ * wave ballots and stores the cell's byte.  Per-cell kernels over all grids at once do the dilation and
+ * the two labellings with the union-find of dp_points.h (west and north links; a root is its component's
+ * first cell), sizes by one atomic per cell.  The roots to fit are numbered by the flag scan of
+ * dp_points.h.  One workgroup per component: a wave per grid row finds the row's leftmost and rightmost
+ * member by ballots; the hull of those (at most 2 * DP_LSHAPE_MAX_SIDE = DP_SHAPES_H_MAX points) is the
+ * component's, so one LDS chunk of the sort, chain and calipers that dp_cluster_shapes runs does it.
+ * Bounds: no kernel waits on another workgroup; no thread loops over the points or over a grid (a wave
+ * walks rows 64 cells at a time; the last kernel's threads walk their rectangles' parts).
+ */
+#define DP_LSHAPE_MAX_SIDE 1024
+int dp_shape_rectangles(const double* shapes, const int32_t* n_clusters_dev, int32_t max_clusters,
+                        double* rects_out, int32_t* n_rects_dev, dp_stream_t stream);
+int64_t dp_lshape_workspace_size(int64_t max_rects, int64_t max_cells);
+int dp_lshape_split(const double* points, const int32_t* labels, const int32_t* n_dev, int32_t n_max,
+                    const double* rects, const int32_t* n_rects_dev, int32_t max_rects, int32_t max_out,
+                    int32_t max_cells, double* rects_out, int32_t* n_out_dev, double* info_out, void* workspace,
+                    int64_t workspace_bytes, dp_stream_t stream);
 
 /* ---- Scale-invariant boundary metric (additive to ABI 20, csrc/dp_boundary.hip) ---------------------
  *

@@ -1,5 +1,5 @@
 // What the point-cloud stages share (dp_ground.hip, dp_clean.hip, dp_cluster.hip, dp_shapes.hip,
-// dp_normals.hip, dp_floorplan.hip): one
+// dp_normals.hip, dp_floorplan.hip, dp_lshape.hip): one
 // copy of every device and host helper that two or more of them use.  A helper with one user stays in
 // its file.  Everything is in an anonymous namespace, so each translation unit has its own copy of the
 // two kernels below.
@@ -130,6 +130,155 @@ __device__ __forceinline__ void uf_unite(uint32_t* p, uint32_t a, uint32_t b) {
     if (a == b) return;
     if (a < b) { const uint32_t t = a; a = b; b = t; }
     if (atomicCAS(&p[a], a, b) == a) return;                     // lost: someone else hooked a; find again
+  }
+}
+
+// number of entries of a[0, n) that are <= v (a ascending)
+__device__ __forceinline__ int upper_bound(const int32_t* __restrict__ a, int n, int v) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (a[mid] <= v) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// ---- convex hull and minimum-area rectangle of one chunk in LDS: rules 2 and 3 of "Cluster shapes" ----
+// For a workgroup of HULL_NT threads (dp_shapes.hip's hull chunks, dp_lshape.hip's occupied components).
+// The caller loads P slots (P a power of two >= m, at most HULL_MAX): m members with st < HULL_PAD and
+// st distinct, the rest st = HULL_PAD, in any order, and passes a barrier.
+constexpr int HULL_NT = 256;
+constexpr int HULL_MAX = DP_SHAPES_H_MAX;
+constexpr uint32_t HULL_PAD = 0xffffffffu;     // the sort's filler: after every member
+constexpr double HULL_DEG = 57.29577951308232; // 180 / pi
+
+struct HullLds {
+  double su[HULL_MAX], sv[HULL_MAX];
+  uint32_t st[HULL_MAX];
+  int lo[HULL_MAX], up[HULL_MAX];
+};
+
+// o(a, b, c) of the header: > 0 for a left turn
+__device__ __forceinline__ double orient(double au, double av, double bu, double bv, double cu, double cv) {
+  return (bu - au) * (cv - av) - (bv - av) * (cu - au);
+}
+
+__device__ __forceinline__ bool hull_before(const HullLds& s, int x, int y) {
+  const uint32_t tx = s.st[x], ty = s.st[y];
+  if (tx == HULL_PAD) return false;
+  if (ty == HULL_PAD) return true;
+  const double ux = s.su[x], uy = s.su[y];
+  if (ux != uy) return ux < uy;
+  const double vx = s.sv[x], vy = s.sv[y];
+  if (vx != vy) return vx < vy;
+  return tx < ty;
+}
+
+// Bitonic sort by (u, v, st), then the monotone chain: the lower hull left to right on wave 0, the
+// upper hull right to left on wave 1.  Only the first of a run of coincident members takes part; a
+// point leaves the stack unless it is a strict left turn.  Returns the number of vertices; vertex e
+// (counter-clockwise from the smallest (u, v)) is slot hull_vertex(s, kl, e).  cnt: 2 shared ints.
+__device__ __forceinline__ int hull_sort_chain(HullLds& s, int m, int P, int* cnt, int* kl_out) {
+  const int tid = threadIdx.x;
+  for (int kk = 2; kk <= P; kk <<= 1)
+    for (int jj = kk >> 1; jj > 0; jj >>= 1) {
+      for (int i = tid; i < (P >> 1); i += HULL_NT) {
+        const int a = 2 * jj * (i / jj) + (i % jj), z = a + jj;
+        const bool asc = (a & kk) == 0;
+        if (asc ? hull_before(s, z, a) : hull_before(s, a, z)) {
+          const double tu = s.su[a], tv = s.sv[a];
+          const uint32_t tt = s.st[a];
+          s.su[a] = s.su[z]; s.sv[a] = s.sv[z]; s.st[a] = s.st[z];
+          s.su[z] = tu; s.sv[z] = tv; s.st[z] = tt;
+        }
+      }
+      __syncthreads();
+    }
+  if (tid == 0 || tid == 64) {
+    int* stack = tid == 0 ? s.lo : s.up;
+    int top = 0;
+    for (int step = 0; step < m; ++step) {
+      const int i = tid == 0 ? step : m - 1 - step;
+      const double cu = s.su[i], cv = s.sv[i];
+      if (i > 0 && s.su[i - 1] == cu && s.sv[i - 1] == cv) continue;
+      while (top >= 2) {
+        const int p1 = stack[top - 1], p0 = stack[top - 2];
+        if (orient(s.su[p0], s.sv[p0], s.su[p1], s.sv[p1], cu, cv) > 0.0) break;
+        --top;
+      }
+      stack[top++] = i;
+    }
+    cnt[tid == 0 ? 0 : 1] = top;
+  }
+  __syncthreads();
+  const int kl = cnt[0], ku = cnt[1];
+  *kl_out = kl;
+  return kl <= 1 ? kl : (kl - 1) + (ku - 1);
+}
+__device__ __forceinline__ int hull_vertex(const HullLds& s, int kl, int e) {
+  return e < kl - 1 || kl <= 1 ? s.lo[e] : s.up[e - (kl - 1)];
+}
+
+// Rule 3 over the hn vertices at the front of s.su / s.sv (the caller has moved them there and passed
+// a barrier; the stacks are free): one edge per lane, the extents of every vertex along e and n, the
+// smallest area with ties to the smallest edge.  One thread writes out[0..6) = centre u, centre v,
+// width, height, angle, area; hn < 2: a 0 x 0 rectangle at the first vertex.  No barrier after the write.
+__device__ __forceinline__ void hull_min_rect(HullLds& s, int hn, double* out) {
+  const int tid = threadIdx.x;
+  double best = __builtin_inf();
+  int besti = 0x7fffffff;
+  double bw = 0.0, bh = 0.0, bcu = 0.0, bcv = 0.0, beu = 1.0, bev = 0.0;
+  if (hn >= 2) {
+    for (int i = tid; i < hn; i += HULL_NT) {
+      const int i1 = i + 1 < hn ? i + 1 : 0;
+      const double du = s.su[i1] - s.su[i], dv = s.sv[i1] - s.sv[i];
+      const double len = __builtin_sqrt(du * du + dv * dv);
+      const double eu = du / len, ev = dv / len;
+      double pmn = __builtin_inf(), pmx = -__builtin_inf(), qmn = __builtin_inf(), qmx = -__builtin_inf();
+      for (int v = 0; v < hn; ++v) {
+        const double u_ = s.su[v], v_ = s.sv[v];
+        const double p = u_ * eu + v_ * ev, q = v_ * eu - u_ * ev;
+        pmn = p < pmn ? p : pmn; pmx = p > pmx ? p : pmx;
+        qmn = q < qmn ? q : qmn; qmx = q > qmx ? q : qmx;
+      }
+      const double w = pmx - pmn, hh = qmx - qmn, a = w * hh;
+      if (a < best) {                                            // a lane's edges come in increasing i
+        best = a; besti = i; bw = w; bh = hh; beu = eu; bev = ev;
+        const double pc = (pmn + pmx) / 2.0, qc = (qmn + qmx) / 2.0;
+        bcu = eu * pc - ev * qc;
+        bcv = ev * pc + eu * qc;
+      }
+    }
+  }
+  double* ra = (double*)s.lo;
+  int* ri = s.up;
+  ra[tid] = best;
+  ri[tid] = besti;
+  __syncthreads();
+  for (int o = HULL_NT / 2; o > 0; o >>= 1) {
+    if (tid < o) {
+      const double a2 = ra[tid + o];
+      const int i2 = ri[tid + o];
+      if (a2 < ra[tid] || (a2 == ra[tid] && i2 < ri[tid])) { ra[tid] = a2; ri[tid] = i2; }
+    }
+    __syncthreads();
+  }
+  const int win = ri[0];
+  if (tid == 0 && (hn < 2 || win == 0x7fffffff)) {               // one vertex (or nothing comparable): 0 x 0 at p0
+    out[0] = s.su[0]; out[1] = s.sv[0];
+    out[2] = out[3] = out[4] = out[5] = 0.0;
+  }
+  if (hn >= 2 && win != 0x7fffffff && besti == win) {
+    double ang = atan2(bev, beu) * HULL_DEG;
+    double kq = __builtin_floor(ang / 90.0);
+    ang = ang - 90.0 * kq;
+    if (ang >= 90.0) { ang = 0.0; kq = kq + 1.0; }               // a tiny negative angle rounds up to 90
+    const bool swap = __builtin_fmod(kq, 2.0) != 0.0;
+    out[0] = bcu; out[1] = bcv;
+    out[2] = swap ? bh : bw;
+    out[3] = swap ? bw : bh;
+    out[4] = ang;
+    out[5] = best;
   }
 }
 

@@ -17,12 +17,11 @@
 
 namespace {
 
-constexpr int NT = 256;
-constexpr int CHUNK = DP_SHAPES_H_MAX;          // members of one hull chunk; also the cap on hull vertices
+constexpr int NT = HULL_NT;
+constexpr int CHUNK = HULL_MAX;                 // members of one hull chunk; also the cap on hull vertices
 constexpr int ROUNDS = 6;                       // hull rounds when one chunk cannot hold every cluster
 constexpr int LM_EVALS = 50;                    // the circle iteration's cap on trial centres
-constexpr uint32_t PAD = 0xffffffffu;           // the sort's filler: after every member
-constexpr double DEG = 57.29577951308232;       // 180 / pi
+constexpr uint32_t PAD = HULL_PAD;
 constexpr double PI = 3.141592653589793;
 
 struct SHdr {
@@ -48,21 +47,6 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
   const double s = ((red[0] + red[1]) + red[2]) + red[3];
   __syncthreads();
   return s;
-}
-
-// number of entries of a[0, n) that are <= v (a ascending)
-__device__ __forceinline__ int upper_bound(const int32_t* __restrict__ a, int n, int v) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (a[mid] <= v) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
-// o(a, b, c) of the header: > 0 for a left turn
-__device__ __forceinline__ double orient(double au, double av, double bu, double bv, double cu, double cv) {
-  return (bu - au) * (cv - av) - (bv - av) * (cu - au);
 }
 
 // ---- gather and row reset -----------------------------------------------------------------------
@@ -145,23 +129,7 @@ __global__ void __launch_bounds__(NT) plan_kernel(int round, const int32_t* __re
 }
 
 // ---- one hull chunk per workgroup ---------------------------------------------------------------
-struct Lds {
-  double su[CHUNK], sv[CHUNK];
-  uint32_t st[CHUNK];
-  int lo[CHUNK], up[CHUNK];
-};
-
-__device__ __forceinline__ bool before(const Lds& s, int x, int y) {
-  const uint32_t tx = s.st[x], ty = s.st[y];
-  if (tx == PAD) return false;
-  if (ty == PAD) return true;
-  const double ux = s.su[x], uy = s.su[y];
-  if (ux != uy) return ux < uy;
-  const double vx = s.sv[x], vy = s.sv[y];
-  if (vx != vy) return vx < vy;
-  return tx < ty;
-}
-
+// (the chunk's LDS, its sort, chain and calipers: dp_points.h)
 __global__ void __launch_bounds__(NT) hull_kernel(int round, const double2* __restrict__ guv, const uint32_t* __restrict__ order,
                                                   const int32_t* __restrict__ offsets, const int32_t* n_dev, int n_max,
                                                   const int32_t* ncl, int max_clusters, const SHdr* h,
@@ -172,7 +140,7 @@ __global__ void __launch_bounds__(NT) hull_kernel(int round, const double2* __re
                                                   int32_t* __restrict__ ocnt, uint32_t* __restrict__ hstage,
                                                   int32_t* __restrict__ hcnt, int32_t* __restrict__ done,
                                                   double* __restrict__ shapes) {
-  __shared__ Lds s;
+  __shared__ HullLds s;
   __shared__ double red[4];
   __shared__ int cnt[2];
   const int cur = round & 1, tid = threadIdx.x;
@@ -215,45 +183,10 @@ __global__ void __launch_bounds__(NT) hull_kernel(int round, const double2* __re
   }
   __syncthreads();
 
-  // bitonic sort by (u, v, position): a position is a row rank inside the cluster, so coincident
-  // members come smallest row first
-  for (int kk = 2; kk <= P; kk <<= 1)
-    for (int jj = kk >> 1; jj > 0; jj >>= 1) {
-      for (int i = tid; i < (P >> 1); i += NT) {
-        const int a = 2 * jj * (i / jj) + (i % jj), z = a + jj;
-        const bool asc = (a & kk) == 0;
-        if (asc ? before(s, z, a) : before(s, a, z)) {
-          const double tu = s.su[a], tv = s.sv[a];
-          const uint32_t tt = s.st[a];
-          s.su[a] = s.su[z]; s.sv[a] = s.sv[z]; s.st[a] = s.st[z];
-          s.su[z] = tu; s.sv[z] = tv; s.st[z] = tt;
-        }
-      }
-      __syncthreads();
-    }
-
-  // monotone chain: the lower hull left to right on wave 0, the upper hull right to left on wave 1.
-  // Only the first of a run of coincident members takes part; a point leaves the stack unless it is
-  // a strict left turn.
-  if (tid == 0 || tid == 64) {
-    int* stack = tid == 0 ? s.lo : s.up;
-    int top = 0;
-    for (int step = 0; step < m; ++step) {
-      const int i = tid == 0 ? step : m - 1 - step;
-      const double cu = s.su[i], cv = s.sv[i];
-      if (i > 0 && s.su[i - 1] == cu && s.sv[i - 1] == cv) continue;
-      while (top >= 2) {
-        const int p1 = stack[top - 1], p0 = stack[top - 2];
-        if (orient(s.su[p0], s.sv[p0], s.su[p1], s.sv[p1], cu, cv) > 0.0) break;
-        --top;
-      }
-      stack[top++] = i;
-    }
-    cnt[tid == 0 ? 0 : 1] = top;
-  }
-  __syncthreads();
-  const int kl = cnt[0], ku = cnt[1];
-  const int hn = kl <= 1 ? kl : (kl - 1) + (ku - 1);            // counter-clockwise from the smallest (u, v)
+  // sort by (u, v, position): a position is a row rank inside the cluster, so coincident members come
+  // smallest row first; then the chain
+  int kl;
+  const int hn = hull_sort_chain(s, m, P, cnt, &kl);            // counter-clockwise from the smallest (u, v)
 
   // the hull's members into registers (CHUNK / NT = 8 per thread)
   double hu[CHUNK / NT], hv[CHUNK / NT];
@@ -264,7 +197,7 @@ __global__ void __launch_bounds__(NT) hull_kernel(int round, const double2* __re
     hu[r] = hv[r] = 0.0;
     ht[r] = 0;
     if (e < hn) {
-      const int i = e < kl - 1 || kl <= 1 ? s.lo[e] : s.up[e - (kl - 1)];
+      const int i = hull_vertex(s, kl, e);
       hu[r] = s.su[i]; hv[r] = s.sv[i]; ht[r] = s.st[i];
     }
   }
@@ -297,69 +230,13 @@ __global__ void __launch_bounds__(NT) hull_kernel(int round, const double2* __re
   for (int i = 1 + tid; i < hn - 1; i += NT) part += orient(s.su[0], s.sv[0], s.su[i], s.sv[i], s.su[i + 1], s.sv[i + 1]);
   const double area2 = block_sum(part, red);
 
-  // rule 3: one edge per lane, the extents of every vertex along e and n
-  double best = __builtin_inf();
-  int besti = 0x7fffffff;
-  double bw = 0.0, bh = 0.0, bcu = 0.0, bcv = 0.0, beu = 1.0, bev = 0.0;
-  if (hn >= 2) {
-    for (int i = tid; i < hn; i += NT) {
-      const int i1 = i + 1 < hn ? i + 1 : 0;
-      const double du = s.su[i1] - s.su[i], dv = s.sv[i1] - s.sv[i];
-      const double len = __builtin_sqrt(du * du + dv * dv);
-      const double eu = du / len, ev = dv / len;
-      double pmn = __builtin_inf(), pmx = -__builtin_inf(), qmn = __builtin_inf(), qmx = -__builtin_inf();
-      for (int v = 0; v < hn; ++v) {
-        const double u_ = s.su[v], v_ = s.sv[v];
-        const double p = u_ * eu + v_ * ev, q = v_ * eu - u_ * ev;
-        pmn = p < pmn ? p : pmn; pmx = p > pmx ? p : pmx;
-        qmn = q < qmn ? q : qmn; qmx = q > qmx ? q : qmx;
-      }
-      const double w = pmx - pmn, hh = qmx - qmn, a = w * hh;
-      if (a < best) {                                            // a lane's edges come in increasing i
-        best = a; besti = i; bw = w; bh = hh; beu = eu; bev = ev;
-        const double pc = (pmn + pmx) / 2.0, qc = (qmn + qmx) / 2.0;
-        bcu = eu * pc - ev * qc;
-        bcv = ev * pc + eu * qc;
-      }
-    }
-  }
-  // smallest area, ties to the smallest edge: through LDS (the stacks are free now)
-  double* ra = (double*)s.lo;
-  int* ri = s.up;
-  ra[tid] = best;
-  ri[tid] = besti;
-  __syncthreads();
-  for (int o = NT / 2; o > 0; o >>= 1) {
-    if (tid < o) {
-      const double a2 = ra[tid + o];
-      const int i2 = ri[tid + o];
-      if (a2 < ra[tid] || (a2 == ra[tid] && i2 < ri[tid])) { ra[tid] = a2; ri[tid] = i2; }
-    }
-    __syncthreads();
-  }
-  const int win = ri[0];
   if (tid == 0) {
     hcnt[c] = hn;
     done[c] = 1;
     row[12] = area2 / 2.0;
     row[13] = (double)hn;
-    if (hn < 2 || win == 0x7fffffff) {                           // one vertex (or nothing comparable): 0 x 0 at p0
-      row[2] = s.su[0]; row[3] = s.sv[0];
-      row[4] = row[5] = row[6] = row[7] = 0.0;
-    }
   }
-  if (hn >= 2 && win != 0x7fffffff && besti == win) {
-    double ang = atan2(bev, beu) * DEG;
-    double kq = __builtin_floor(ang / 90.0);
-    ang = ang - 90.0 * kq;
-    if (ang >= 90.0) { ang = 0.0; kq = kq + 1.0; }               // a tiny negative angle rounds up to 90
-    const bool swap = __builtin_fmod(kq, 2.0) != 0.0;
-    row[2] = bcu; row[3] = bcv;
-    row[4] = swap ? bh : bw;
-    row[5] = swap ? bw : bh;
-    row[6] = ang;
-    row[7] = best;
-  }
+  hull_min_rect(s, hn, row + 2);                                 // rule 3: centre, width, height, angle, area
 }
 
 // ---- circle and decision: one workgroup per cluster -----------------------------------------------

@@ -32,6 +32,7 @@ DP_GROUND_MAX_SEG, DP_GROUND_MAX_GRID = 1024, 32
 DP_FLOOR_MAX_DIM, DP_FLOOR_MAX_KERNEL, DP_FLOOR_COLUMNS = 8192, 15, 13
 DP_BOUNDARY_MAX_DIM, DP_BOUNDARY_MAX_T, DP_BOUNDARY_DIRS, DP_BOUNDARY_COUNTS = 16384, 32, 4, 3
 DP_BOUNDARY_DEPTH, DP_BOUNDARY_MASK, DP_BOUNDARY_INVERSE, DP_BOUNDARY_SEGMENT = 0, 1, 2, 64
+DP_LSHAPE_MAX_SIDE = 1024
 DP_ABI_VERSION = 20
 
 _ERRORS = {1000: "DP_ERR_ARG", 1001: "DP_ERR_SHAPE", 1002: "DP_ERR_ALIGN", 1003: "DP_ERR_DTYPE"}
@@ -54,6 +55,7 @@ EXPORTS = (
     "dp_shapes_workspace_size", "dp_cluster_shapes",
     "dp_normals_workspace_size", "dp_voxel_downsample", "dp_knn_search", "dp_estimate_normals",
     "dp_floorplan_workspace_size", "dp_occupancy_grid", "dp_grid_morphology", "dp_grid_regions", "dp_floorplan_image",
+    "dp_shape_rectangles", "dp_lshape_workspace_size", "dp_lshape_split",
     "dp_boundary_workspace_size", "dp_boundary_counts", "dp_boundary_edges",
 )
 
@@ -164,6 +166,9 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "dp_grid_morphology": [vp, vp, i32, i32, i32, i32, vp, vp, i64, vp],
         "dp_grid_regions": [vp, vp, vp, vp, vp, i32, f64, i32, vp, vp, vp, vp, vp, i64, vp],
         "dp_floorplan_image": [vp, vp, i32, vp, vp, i32, f64, f64, f64, i32, vp, vp],
+        "dp_shape_rectangles": [vp, vp, i32, vp, vp, vp],
+        "dp_lshape_workspace_size": [i64, i64],
+        "dp_lshape_split": [vp, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, i64, vp],
         "dp_boundary_workspace_size": [i32, i32, i32],
         "dp_boundary_counts": [vp, i64, vp, i64, i32, i32, i32, ctypes.POINTER(f64), i32, vp, vp, i64, vp],
         "dp_boundary_edges": [vp, i64, i32, i32, f64, i32, vp, vp, i64, vp],
@@ -179,6 +184,7 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.dp_shapes_workspace_size.restype = ctypes.c_int64
     lib.dp_normals_workspace_size.restype = ctypes.c_int64
     lib.dp_floorplan_workspace_size.restype = ctypes.c_int64
+    lib.dp_lshape_workspace_size.restype = ctypes.c_int64
     lib.dp_boundary_workspace_size.restype = ctypes.c_int64
     lib.dp_gemm_debug_flags.argtypes = [ctypes.c_int]
     lib.dp_gemm_debug_flags.restype = ctypes.c_int

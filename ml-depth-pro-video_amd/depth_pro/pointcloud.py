@@ -694,13 +694,93 @@ def split_large_rectangle(cu: float, cv: float, width: float, height: float, ang
             (cu + d * np.sin(a), cv - d * np.cos(a), width, height / 2, angle)]
 
 
-def shape_summary(shapes_host, params: Optional[dict] = None) -> dict:
+# ---- the rectangle list and the L-shape split (csrc/dp_lshape.hip) ----------------------------------
+
+RECT_COLUMNS = ("cu", "cv", "width", "height", "angle", "cluster", "flags", "reserved")
+RECT_HALF, RECT_L_PART = 1, 2          # bits of the flags column
+LSHAPE_STATUS = ("split", "small", "few_points", "thin", "no_empty_region", "empty_ratio", "one_part", "few_parts",
+                 "area_ratio", "capacity")
+LSHAPE_INFO = ("status", "points_inside", "grid_width", "grid_height", "empty_cells", "occupied_parts", "parts_listed",
+               "error")
+LSHAPE_MAX_SIDE = _lib.DP_LSHAPE_MAX_SIDE
+_LSHAPE = "the L-shape split runs on the ROCm device (csrc/dp_lshape.hip)"
+
+
+def rectangle_list(shapes: torch.Tensor, n_clusters: torch.Tensor, max_clusters: int = 4096
+                   ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`dp_shape_rectangles`: the rectangle list the reference's `fit_shapes_to_clusters` builds from the
+    (max_clusters, 16) table of `fit_shapes` -- every rectangle row in cluster order, one with width * height >
+    100 and more than 1000 members as its two halves (`split_large_rectangle`).  Returns (rects
+    (2 * max_clusters, 8) float64 in `RECT_COLUMNS` order, device int32 count).  On the device, asynchronous."""
+    mc = int(max_clusters)
+    if mc < 0:
+        raise ValueError(f"max_clusters must be >= 0 (got {max_clusters})")
+    if not torch.is_tensor(shapes) or shapes.device.type != "cuda":
+        raise _lib.DPError(_LSHAPE)
+    if shapes.dtype != torch.float64 or tuple(shapes.shape) != (mc, 16) or not shapes.is_contiguous():
+        raise ValueError("shapes must be a contiguous (max_clusters, 16) float64 tensor")
+    if not torch.is_tensor(n_clusters) or n_clusters.device != shapes.device:
+        raise _lib.DPError("n_clusters must be on the shapes' device")
+    if n_clusters.dtype != torch.int32 or n_clusters.numel() != 1:
+        raise ValueError("n_clusters must be a device int32 scalar")
+    rects = torch.zeros(2 * mc, 8, dtype=torch.float64, device=shapes.device)
+    n_rects = torch.zeros((), dtype=torch.int32, device=shapes.device)
+    stream = torch.cuda.current_stream(shapes.device).cuda_stream
+    check(_lib.load().dp_shape_rectangles(shapes.data_ptr(), n_clusters.data_ptr(), mc, rects.data_ptr(),
+                                          n_rects.data_ptr(), stream), "dp_shape_rectangles")
+    return rects, n_rects
+
+
+def split_l_shapes(points: torch.Tensor, labels: torch.Tensor, rects: torch.Tensor, n_rects: torch.Tensor, count=None,
+                   max_out: Optional[int] = None, max_cells: int = 1 << 20
+                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """`dp_lshape_split`: the reference's `detect_and_split_l_shapes` on a rectangle list (`rectangle_list`, or
+    any (R, 8) rows in `RECT_COLUMNS` order with a device int32 count) against the DBSCAN participants of
+    `labels` (every row with label >= -1).  Returns (rects_out (max_out, 8) float64, n_out (2,) int32 =
+    (rows, error word), info (R, 8) float64 in `LSHAPE_INFO` order, one row per input rectangle).  `max_out`
+    defaults to R + 4096 rows; `max_cells` is the capacity of all the rectangles' 0.2 m grids together.
+    On the device, asynchronous, no read-back."""
+    lib, pts, n, count, cptr, stream = _points_args(points, count, _LSHAPE)
+    for t in (labels, rects, n_rects):
+        if not torch.is_tensor(t) or t.device != pts.device:
+            raise _lib.DPError("labels, rects and n_rects must be on the points' device")
+    if labels.dtype != torch.int32 or tuple(labels.shape) != (n,) or not labels.is_contiguous():
+        raise ValueError("labels must be a contiguous (N,) int32 tensor")
+    if rects.dtype != torch.float64 or rects.dim() != 2 or rects.shape[1] != 8 or not rects.is_contiguous():
+        raise ValueError("rects must be a contiguous (R, 8) float64 tensor")
+    if n_rects.dtype != torch.int32 or n_rects.numel() != 1:
+        raise ValueError("n_rects must be a device int32 scalar")
+    mr = rects.shape[0]
+    mo = mr + 4096 if max_out is None else int(max_out)
+    mcells = int(max_cells)
+    if mo < 0 or mcells < 0 or mcells >= 2 ** 31 or mo >= 2 ** 27:
+        raise ValueError(f"max_out and max_cells must be >= 0 and in range (got {max_out}, {max_cells})")
+    ws = torch.empty(int(lib.dp_lshape_workspace_size(mr, mcells)), dtype=torch.uint8, device=pts.device)
+    out = torch.zeros(mo, 8, dtype=torch.float64, device=pts.device)
+    n_out = torch.zeros(2, dtype=torch.int32, device=pts.device)
+    info = torch.zeros(mr, 8, dtype=torch.float64, device=pts.device)
+    check(lib.dp_lshape_split(pts.data_ptr(), labels.data_ptr(), cptr, n, rects.data_ptr(), n_rects.data_ptr(), mr, mo,
+                              mcells, out.data_ptr(), n_out.data_ptr(), info.data_ptr(), ws.data_ptr(), ws.numel(), stream),
+          "dp_lshape_split")
+    return out, n_out, info
+
+
+def shape_summary(shapes_host, params: Optional[dict] = None, rects_host=None, info_host=None) -> dict:
     """The `{base}_shapes.json` content from the (K, 16) rows of `fit_shapes` already on the host:
     parameters, counts, and the `rectangles` and `circles` lists in cluster order, as the reference's
     `fit_shapes_to_clusters` builds them -- a rectangle with width * height > 100 and more than 1000
     members is split in two (`split_large_rectangle`), each half marked `"split": true`.
+    With `rects_host` (the written rows of `split_l_shapes`' output) and `info_host` (its info rows, one per
+    input rectangle) the rectangles are listed from `rects_host` instead -- the reference's list after
+    `detect_and_split_l_shapes` -- each with `"l_part"`, and the summary gains `"l_split": true` and an
+    `"l_shapes"` block: per input rectangle the status name and the `LSHAPE_INFO` columns.  Without them
     `detect_and_split_l_shapes` is not applied.  Host only."""
     t = np.asarray(shapes_host, dtype=np.float64).reshape(-1, 16)
+    if (rects_host is None) != (info_host is None):
+        raise ValueError("rects_host and info_host go together")
+    if rects_host is not None:
+        return _shape_summary_split(t, params, np.asarray(rects_host, dtype=np.float64).reshape(-1, 8),
+                                    np.asarray(info_host, dtype=np.float64).reshape(-1, 8))
     rects, circles = [], []
     skipped = errors = 0
     for c, r in enumerate(t):
@@ -722,6 +802,24 @@ def shape_summary(shapes_host, params: Optional[dict] = None) -> dict:
             skipped += 1
     return {"parameters": dict(params or {}), "clusters_listed": len(t), "skipped": skipped, "errors": errors,
             "rectangles": rects, "circles": circles}
+
+
+def _shape_summary_split(t, params, rows, info) -> dict:
+    """`shape_summary` with the rectangle list of `split_l_shapes`."""
+    base = shape_summary(t, params)
+    rects = []
+    for q in rows:
+        c, flags = int(q[5]), int(q[6])
+        r = t[c] if 0 <= c < len(t) else np.zeros(16)
+        rects.append({"cluster": c, "count": int(r[1]), "center": [float(q[0]), float(q[1])], "width": float(q[2]),
+                      "height": float(q[3]), "angle": float(q[4]), "split": bool(flags & RECT_HALF),
+                      "l_part": bool(flags & RECT_L_PART), "hull_area": float(r[12]), "hull_vertices": int(r[13]),
+                      "circularity": float(r[14])})
+    base["rectangles"] = rects
+    base["l_split"] = True
+    base["l_shapes"] = [dict({"status_name": LSHAPE_STATUS[int(i[0])] if 0 <= int(i[0]) < len(LSHAPE_STATUS) else "unknown"},
+                             **{k: int(v) for k, v in zip(LSHAPE_INFO, i)}) for i in info]
+    return base
 
 
 def export_shape_text(summary: dict, path: str) -> None:

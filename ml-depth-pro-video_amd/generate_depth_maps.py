@@ -318,7 +318,7 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                               cluster_height=1.3, cluster_max_points=100000, fit_shapes=False,
                               circularity_threshold=0.85, mesh_points=False, voxel_size=0.05, normals_max_nn=30,
                               floor_plan=False, floor_resolution=0.1, floor_height=1.3, floor_min_area=0.025,
-                              boundary_dir=None):
+                              boundary_dir=None, split_l_shapes=False):
     """Directory loop (reference :153-206), pipelined decode -> GPU -> encode, frame-sharded across ranks.
 
     Every rank writes its own frames' files; each frame has exactly one owner.  resume=True skips
@@ -348,6 +348,8 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
     and circle on the same stream right after the cluster table (`PC.fit_shapes`, with the reference's
     circle-or-rectangle decision at circularity_threshold) and writes `{base}_shapes.json`
     (`PC.shape_summary`) and `{base}_shapes.txt` (the reference's `export_shape_data` layout).
+    split_l_shapes=True (implies fit_shapes) queues the reference's `detect_and_split_l_shapes` behind the
+    shapes (`PC.rectangle_list`, `PC.split_l_shapes`); both files then list the rectangles after the split.
     mesh_points=True (implies clean_pointcloud) turns the cleaned cloud into the oriented point set every meshing
     method of the reference's pointcloud_to_mesh.py starts from (`PC.oriented_points`: voxel grid of voxel_size,
     normals over radius 2 * voxel_size and at most normals_max_nn neighbours, oriented towards the origin) on the
@@ -383,10 +385,12 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
         check_mesh(voxel_size, normals_max_nn)
         clean_pointcloud = True
         mesh = {"voxel_size": float(voxel_size), "max_nn": int(normals_max_nn)}
-    if fit_shapes:
+    if fit_shapes or split_l_shapes:
         check_circularity(circularity_threshold)
         cluster_pointcloud = True
         shapes = {"circularity_threshold": float(circularity_threshold)}
+        if split_l_shapes:
+            shapes["l_split"] = True
     if cluster_pointcloud:
         check_cluster(cluster_eps, cluster_min_samples, cluster_max_points)
         clean_pointcloud = True
@@ -644,6 +648,11 @@ def _points(depth: torch.Tensor, f_px, image, ground=None, image_path=None, clea
         if shapes is not None:
             # the clusters' shapes (--fit_shapes): queued right behind the table; only the small table goes to the host
             extra += (PC.fit_shapes(xyz, order, offsets, ncl, count, MAX_CLUSTERS, shapes["circularity_threshold"])[0],)
+            if shapes.get("l_split"):
+                # the reference's detect_and_split_l_shapes (--split_l_shapes): the rectangle list and its split, queued
+                # right behind the shapes; the small rectangle and info tables go to the host with the rest
+                rects, n_rects = PC.rectangle_list(extra[-1], ncl, MAX_CLUSTERS)
+                extra += PC.split_l_shapes(xyz, labels, rects, n_rects, count) + (n_rects,)
     out = []
     for t in (PC.ply_records_async(xyz, cols), count) + extra:
         hbuf = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
@@ -693,8 +702,14 @@ def _write_shapes(pc, cluster: dict, shapes: dict, json_path: str) -> None:
     import json
 
     k = min(int(pc[3]), MAX_CLUSTERS)
-    params = {key: (None if isinstance(v, float) and v != v else v) for key, v in {**cluster, **shapes}.items()}
-    summary = PC.shape_summary(pc[6][:k].numpy(), params)
+    params = {key: (None if isinstance(v, float) and v != v else v) for key, v in {**cluster, **shapes}.items()
+              if key != "l_split"}
+    if shapes.get("l_split"):
+        rows, n_out, info, n_rects = pc[7:11]
+        summary = PC.shape_summary(pc[6][:k].numpy(), params, rows[:int(n_out[0])].numpy(), info[:int(n_rects)].numpy())
+        summary["l_overflow"] = bool(n_out[1])
+    else:
+        summary = PC.shape_summary(pc[6][:k].numpy(), params)
     with open(json_path, "w") as f:
         json.dump(summary, f, indent=1)
     PC.export_shape_text(summary, os.path.splitext(json_path)[0] + ".txt")
@@ -841,6 +856,10 @@ def main():
     parser.add_argument("--fit_shapes", action="store_true",
                         help="Fit a rectangle or a circle to every cluster (implies --cluster_pointcloud): "
                              "{frame}_shapes.json and the floor-plan text {frame}_shapes.txt")
+    parser.add_argument("--split_l_shapes", action="store_true",
+                        help="Split rectangles that hold separate occupied parts, as the reference's "
+                             "detect_and_split_l_shapes does (implies --fit_shapes): the split list goes to "
+                             "{frame}_shapes.json and {frame}_shapes.txt")
     parser.add_argument("--circularity_threshold", type=float, default=0.85,
                         help="Hull area over circle area above which a cluster may be a circle (default 0.85)")
     parser.add_argument("--mesh_points", action="store_true",
@@ -897,7 +916,8 @@ def main():
                               stray_neighbors=args.stray_neighbors, cluster_pointcloud=args.cluster_pointcloud,
                               cluster_eps=args.cluster_eps, cluster_min_samples=args.cluster_min_samples,
                               cluster_height=args.cluster_height, cluster_max_points=args.cluster_max_points,
-                              fit_shapes=args.fit_shapes, circularity_threshold=args.circularity_threshold,
+                              fit_shapes=args.fit_shapes, split_l_shapes=args.split_l_shapes,
+                              circularity_threshold=args.circularity_threshold,
                               mesh_points=args.mesh_points, voxel_size=args.voxel_size, normals_max_nn=args.normals_max_nn,
                               floor_plan=args.floor_plan, floor_resolution=args.floor_resolution,
                               floor_height=args.floor_height, floor_min_area=args.floor_min_area,

@@ -22,13 +22,14 @@ from __future__ import annotations
 
 import argparse
 import glob
+import inspect
+import json
 import os
-import queue
 import sys
-import threading
 import time
 from concurrent.futures import ThreadPoolExecutor
-from typing import List, Optional, Tuple
+from functools import partial
+from typing import Callable, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -182,16 +183,20 @@ def _encode(depth_np: np.ndarray, output_path: str, colored: bool, cmap: str) ->
     return output_path
 
 
+def _pinned(t: torch.Tensor) -> torch.Tensor:
+    """A pinned host copy of a device tensor, queued on the current stream (no host sync)."""
+    host = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+    host.copy_(t, non_blocking=True)
+    return host
+
+
 def _image_async(depth: torch.Tensor, colored: bool, cmap: str) -> torch.Tensor:
     """The PNG content of a device depth map, made on the GPU (dp_depth_to_image: colorize_depth /
     --raw, byte-identical) and queued into pinned host memory on the current stream (no host
     sync): the writer thread only PNG-encodes it after the frame's event."""
     from depth_pro import ops
 
-    img = ops.depth_to_image(depth.contiguous(), colored=colored, cmap=cmap)
-    host = torch.empty(img.shape, dtype=img.dtype, pin_memory=True)
-    host.copy_(img, non_blocking=True)
-    return host
+    return _pinned(ops.depth_to_image(depth.contiguous(), colored=colored, cmap=cmap))
 
 
 def _host_image(host: torch.Tensor) -> np.ndarray:
@@ -204,8 +209,7 @@ def generate_depth_map(image_path, output_path=None, downscale_factor=1.0, half_
     """One frame (reference :46-151); returns the output path or None on error."""
     try:
         if output_path is None:
-            base_name = os.path.splitext(os.path.basename(image_path))[0]
-            output_path = f"{base_name}_depth.png"
+            output_path = output_name(image_path)
         model, transform = _model(_device(), half_precision)
         image, f_px = _load(image_path, downscale_factor)
         image = _downscale(image, downscale_factor, _device())
@@ -226,88 +230,73 @@ def generate_depth_map(image_path, output_path=None, downscale_factor=1.0, half_
         return None
 
 
-def output_name(image_path: str) -> str:
-    """`{base}_depth.png` (reference :187-188)."""
-    return f"{os.path.splitext(os.path.basename(image_path))[0]}_depth.png"
+def frame_file(image_path: str, suffix: str) -> str:
+    """`{base}{suffix}`: the name of one of a frame's files, from its image path."""
+    return os.path.splitext(os.path.basename(image_path))[0] + suffix
+
+
+# the public names of a frame's files, from its image path
+output_name = partial(frame_file, suffix="_depth.png")                  # reference :187-188
+clusters_name = partial(frame_file, suffix="_clusters.json")            # --cluster_pointcloud; the labels go beside it
+labels_name = partial(frame_file, suffix="_labels.npy")
+shapes_name = partial(frame_file, suffix="_shapes.json")                # --fit_shapes; `{base}_shapes.txt` goes beside it
+oriented_name = partial(frame_file, suffix="_oriented.ply")             # --mesh_points; parameters and statistics beside it
+oriented_json_name = partial(frame_file, suffix="_oriented.json")
+floorplan_name = partial(frame_file, suffix="_floorplan.png")           # --floor_plan; origin, statistics, regions beside it
+floorplan_json_name = partial(frame_file, suffix="_floorplan.json")
+boundary_name = partial(frame_file, suffix="_boundary.json")            # --boundary_dir: the score against `{base}.npy` there
 
 
 def cloud_name(image_path: str, cleaned: bool = False) -> str:
     """`{base}_points.ply`, or `{base}_clean.ply` (the reference cleaner's file name) with --clean_pointcloud."""
-    return f"{os.path.splitext(os.path.basename(image_path))[0]}_{'clean' if cleaned else 'points'}.ply"
-
-
-def clusters_name(image_path: str) -> str:
-    """`{base}_clusters.json` (--cluster_pointcloud); the labels go to `{base}_labels.npy` beside it."""
-    return f"{os.path.splitext(os.path.basename(image_path))[0]}_clusters.json"
-
-
-def labels_name(image_path: str) -> str:
-    return f"{os.path.splitext(os.path.basename(image_path))[0]}_labels.npy"
-
-
-def shapes_name(image_path: str) -> str:
-    """`{base}_shapes.json` (--fit_shapes); the reference's text export goes to `{base}_shapes.txt` beside it."""
-    return f"{os.path.splitext(os.path.basename(image_path))[0]}_shapes.json"
-
-
-def oriented_name(image_path: str) -> str:
-    """`{base}_oriented.ply` (--mesh_points); its parameters and statistics go to `{base}_oriented.json` beside it."""
-    return f"{os.path.splitext(os.path.basename(image_path))[0]}_oriented.ply"
-
-
-def oriented_json_name(image_path: str) -> str:
-    return f"{os.path.splitext(os.path.basename(image_path))[0]}_oriented.json"
-
-
-def floorplan_name(image_path: str) -> str:
-    """`{base}_floorplan.png` (--floor_plan); its origin, parameters, statistics and regions go to
-    `{base}_floorplan.json` beside it."""
-    return f"{os.path.splitext(os.path.basename(image_path))[0]}_floorplan.png"
-
-
-def floorplan_json_name(image_path: str) -> str:
-    return f"{os.path.splitext(os.path.basename(image_path))[0]}_floorplan.json"
-
-
-def boundary_name(image_path: str) -> str:
-    """`{base}_boundary.json` (--boundary_dir): the frame's boundary score against `{base}.npy` of that directory."""
-    return f"{os.path.splitext(os.path.basename(image_path))[0]}_boundary.json"
+    return frame_file(image_path, "_clean.ply" if cleaned else "_points.ply")
 
 
 def boundary_target_path(image_path: str, boundary_dir: str) -> str:
-    return os.path.join(boundary_dir, f"{os.path.splitext(os.path.basename(image_path))[0]}.npy")
+    return os.path.join(boundary_dir, frame_file(image_path, ".npy"))
 
 
 def plan_frames(image_paths, output_dir: str, world: int, rank: int, resume: bool, cleaned: bool = False,
                 clustered: bool = False, shaped: bool = False, oriented: bool = False, floor: bool = False,
-                boundary: Optional[str] = None) -> List[int]:
+                boundary: Optional[str] = None, stages=()) -> List[int]:
     """Indices of the frames this rank processes: the frames still to do (all of them, or with
-    `resume` those whose output file is missing -- decided by rank 0 alone and broadcast before
+    `resume` those with an output file missing -- decided by rank 0 alone and broadcast before
     any rank writes, so every rank shards the same list), dealt round-robin over the ranks.
-    `cleaned` (--clean_pointcloud): a frame also counts as missing without its `{base}_clean.ply`;
-    `clustered` (--cluster_pointcloud): and without its `{base}_clusters.json`; `shaped` (--fit_shapes): and
-    without its `{base}_shapes.json`; `oriented` (--mesh_points): and without its `{base}_oriented.ply` or
-    `{base}_oriented.json`; `floor` (--floor_plan): and without its `{base}_floorplan.png` or `{base}_floorplan.json`;
-    `boundary` (--boundary_dir): a frame with a target `{base}.npy` in that directory, and without its `{base}_boundary.json`."""
+    Missing: a frame without its `{base}_depth.png`, or without a file that a stage which is on requires
+    (`Stage.suffixes`).  On are the stages named in `stages`, and `cleaned` (--clean_pointcloud), `clustered`
+    (--cluster_pointcloud), `shaped` (--fit_shapes), `oriented` (--mesh_points), `floor` (--floor_plan), `boundary`
+    (--boundary_dir: only a frame with a target `{base}.npy` in that directory needs its `{base}_boundary.json`)."""
     todo = list(range(len(image_paths)))
     if resume:
         if rank == 0:
-            done = lambda k: os.path.exists(os.path.join(output_dir, output_name(image_paths[k]))) and (   # noqa: E731
-                not cleaned or os.path.exists(os.path.join(output_dir, cloud_name(image_paths[k], True)))) and (
-                not clustered or os.path.exists(os.path.join(output_dir, clusters_name(image_paths[k])))) and (
-                not shaped or os.path.exists(os.path.join(output_dir, shapes_name(image_paths[k])))) and (
-                not oriented or (os.path.exists(os.path.join(output_dir, oriented_name(image_paths[k]))) and
-                                 os.path.exists(os.path.join(output_dir, oriented_json_name(image_paths[k]))))) and (
-                not floor or (os.path.exists(os.path.join(output_dir, floorplan_name(image_paths[k]))) and
-                              os.path.exists(os.path.join(output_dir, floorplan_json_name(image_paths[k]))))) and (
-                not boundary or not os.path.exists(boundary_target_path(image_paths[k], boundary)) or
-                os.path.exists(os.path.join(output_dir, boundary_name(image_paths[k]))))
+            on = set(stages) | {name for name, flag in (("clean", cleaned), ("cluster", clustered), ("shapes", shaped),
+                                                        ("mesh", oriented), ("floor", floor), ("boundary", boundary)) if flag}
+            need = ["_depth.png"] + [s for st in STAGES if st.name in on and st.name != "boundary" for s in st.suffixes]
+
+            def done(k):
+                have = lambda s: os.path.exists(os.path.join(output_dir, frame_file(image_paths[k], s)))   # noqa: E731
+                return all(have(s) for s in need) and (
+                    not boundary or not os.path.exists(boundary_target_path(image_paths[k], boundary)) or have("_boundary.json"))
             todo = [k for k in todo if not done(k)]
         if world > 1:
             box = [todo]
             dist.broadcast_object_list(box, src=0)
             todo = box[0]
     return [todo[i] for i in D.shard_frames(len(todo), rank, world)]
+
+
+def resolve_stages(**options) -> dict:
+    """The stages a run has on, from the loop's options (`batch_generate_depth_maps`'s keywords; one left out has
+    its default): {stage name: its parameter dict}, in the order of `STAGES`.  A stage is on when its own option is,
+    or when a stage that is on implies it; the options of the stages that are on are checked (ValueError), the
+    others are not looked at.  Touches no GPU and no file (but `check_boundary_dir`'s isdir)."""
+    o = {**_DEFAULTS, **options}
+    on = set()
+    for st in reversed(STAGES):             # a stage stands behind every stage it implies
+        if st.name in on or st.on(o):
+            on |= {st.name, st.implies} - {None}
+    params = {st.name: st.params(o) for st in reversed(STAGES) if st.name in on}
+    return {st.name: params[st.name] for st in STAGES if st.name in on}
 
 
 def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_factor=1.0, half_precision=False,
@@ -322,10 +311,14 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
     """Directory loop (reference :153-206), pipelined decode -> GPU -> encode, frame-sharded across ranks.
 
     Every rank writes its own frames' files; each frame has exactly one owner.  resume=True skips
-    frames whose `{base}_depth.png` already exists (checkpoint/resume row).
+    frames whose `{base}_depth.png` already exists (checkpoint/resume row) and, with a stage on,
+    that stage's files too.  `model`: an already-built (model, transform) pair (tests); default: `_model`.
+    Returns the number of frames this rank wrote.  The stages (`STAGES`), each queued on the frame's stream
+    like every other output; without a stage the loop writes exactly what it wrote before:
     pointcloud=True also writes `{base}_points.ply` per frame: the reference's depth_to_3d
     back-projection with the frame's focal length (EXIF, or the FOV head's) and RGB colours
-    (SURVEY 8f).  normalize_ground=True (implies pointcloud) levels that cloud first, as the
+    (SURVEY 8f).
+    normalize_ground=True (implies pointcloud) levels that cloud first, as the
     reference's img_to_normalized_pointcloud.py does per image (:1228-1287): ground plane at y = 0
     (`PC.normalize_to_ground`), then the per-cell adjustment (`PC.ground_adjust` with grid_size /
     ground_percentile); same point order and colours, same writer path.  Video semantics (ours): the
@@ -336,86 +329,44 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
     applied to the plane in use, not to the saved file, so a re-run does not rotate twice.
     clean_pointcloud=True (implies normalize_ground) then cleans the levelled cloud on the GPU as the
     reference pipeline's next step does (`PC.clean_pointcloud`: remove_stray_points with stray_neighbors /
-    stray_radius, then clean_shadows) and writes `{base}_clean.ply` in place of `{base}_points.ply`;
-    resume=True then also looks for that file.
+    stray_radius, then clean_shadows) and writes `{base}_clean.ply` in place of `{base}_points.ply`.
     cluster_pointcloud=True (implies clean_pointcloud) clusters the cleaned cloud's top-down projection as
     the reference's floor-plan step does (`PC.cluster_pointcloud`: DBSCAN with cluster_eps /
     cluster_min_samples over the points with y >= cluster_height -- NaN: every height --, thinned to
     cluster_max_points, 0 = all) and writes `{base}_clusters.json` (parameters, counts, per-cluster count,
     bounding box, centroid, smallest core row) and `{base}_labels.npy` (int32, in the row order of
-    `{base}_clean.ply`) beside the cloud; queued on the frame's stream like every other output.
+    `{base}_clean.ply`) beside the cloud.
     fit_shapes=True (implies cluster_pointcloud) fits each cluster's convex hull, minimum-area rectangle
-    and circle on the same stream right after the cluster table (`PC.fit_shapes`, with the reference's
+    and circle right after the cluster table (`PC.fit_shapes`, with the reference's
     circle-or-rectangle decision at circularity_threshold) and writes `{base}_shapes.json`
     (`PC.shape_summary`) and `{base}_shapes.txt` (the reference's `export_shape_data` layout).
     split_l_shapes=True (implies fit_shapes) queues the reference's `detect_and_split_l_shapes` behind the
     shapes (`PC.rectangle_list`, `PC.split_l_shapes`); both files then list the rectangles after the split.
-    mesh_points=True (implies clean_pointcloud) turns the cleaned cloud into the oriented point set every meshing
-    method of the reference's pointcloud_to_mesh.py starts from (`PC.oriented_points`: voxel grid of voxel_size,
-    normals over radius 2 * voxel_size and at most normals_max_nn neighbours, oriented towards the origin) on the
-    same stream and writes `{base}_oriented.ply` (double x y z nx ny nz + uchar rgb) and `{base}_oriented.json`
-    (parameters, point count, both statistics); without it the loop writes exactly what it wrote before.
     floor_plan=True (implies clean_pointcloud) makes the reference's occupancy floor plan of the cleaned cloud
     (`PC.floor_plan`: the rows with y >= floor_height -- NaN: every height -- rasterised at floor_resolution, closing
-    7 x 7 twice, opening 3 x 3, 8-connected regions, regions of at least floor_min_area m^2 drawn) on the same stream
+    7 x 7 twice, opening 3 x 3, 8-connected regions, regions of at least floor_min_area m^2 drawn)
     and writes `{base}_floorplan.png` (RGB, row 0 = smallest z) and `{base}_floorplan.json` (origin, resolution, size,
-    parameters, statistics, one object per drawn region); without it the loop writes exactly what it wrote before.
+    parameters, statistics, one object per drawn region).
+    mesh_points=True (implies clean_pointcloud) turns the cleaned cloud into the oriented point set every meshing
+    method of the reference's pointcloud_to_mesh.py starts from (`PC.oriented_points`: voxel grid of voxel_size,
+    normals over radius 2 * voxel_size and at most normals_max_nn neighbours, oriented towards the origin)
+    and writes `{base}_oriented.ply` (double x y z nx ny nz + uchar rgb) and `{base}_oriented.json`
+    (parameters, point count, both statistics).
     boundary_dir=DIR scores each frame whose target `DIR/{base}.npy` exists and has the depth's shape with the Depth Pro
-    boundary metric (`depth_pro.eval.boundary_metrics`), from the device depth before its read-back, on the same stream:
+    boundary metric (`depth_pro.eval.boundary_metrics`), from the device depth before its read-back:
     a float32 target is a depth (SI_boundary_F1), a bool or uint8 one a mask (SI_boundary_Recall, the raw values
     thresholded by > 0.1).  `{base}_boundary.json` holds the kind, the score, the per-threshold counts, the thresholds,
     H and W; a missing or unusable target is reported and the frame goes on without a score; rank 0 prints the mean.
-    `model`: an already-built (model, transform) pair (tests); default: `_model`.
-    Returns the number of frames this rank wrote.
     """
-    ground = None
-    clean = None
-    cluster = None
-    shapes = None
-    mesh = None
-    floor = None
-    if boundary_dir is not None:
-        check_boundary_dir(boundary_dir)
-    scores = []
-    if floor_plan:
-        check_floor(floor_resolution, floor_height, floor_min_area)
-        clean_pointcloud = True
-        floor = {"resolution": float(floor_resolution), "height_threshold": float(floor_height), "min_area": float(floor_min_area)}
-    if mesh_points:
-        check_mesh(voxel_size, normals_max_nn)
-        clean_pointcloud = True
-        mesh = {"voxel_size": float(voxel_size), "max_nn": int(normals_max_nn)}
-    if fit_shapes or split_l_shapes:
-        check_circularity(circularity_threshold)
-        cluster_pointcloud = True
-        shapes = {"circularity_threshold": float(circularity_threshold)}
-        if split_l_shapes:
-            shapes["l_split"] = True
-    if cluster_pointcloud:
-        check_cluster(cluster_eps, cluster_min_samples, cluster_max_points)
-        clean_pointcloud = True
-        cluster = {"eps": float(cluster_eps), "min_samples": int(cluster_min_samples),
-                   "height_threshold": float(cluster_height), "max_points": int(cluster_max_points)}
-    if clean_pointcloud:
-        check_stray(stray_radius, stray_neighbors)
-        normalize_ground = True
-        clean = {"radius": float(stray_radius), "nb": int(stray_neighbors)}
-    if normalize_ground:
-        check_grid_size(grid_size)
-        pointcloud = True
-        ground = {"model": None, "dir": ground_params_dir or output_dir, "grid": int(grid_size),
-                  "pct": ground_percentile, "rot": rotation_offset, "resolved": False}
+    params = resolve_stages(**{k: v for k, v in locals().items() if k in _DEFAULTS}, output_dir=output_dir)
+    on = [st for st in STAGES if st.name in params]
     os.makedirs(output_dir, exist_ok=True)
     image_paths = sorted(glob.glob(os.path.join(input_dir, pattern)))
     if not image_paths:
         print(f"No images found matching pattern {os.path.join(input_dir, pattern)}")
         return 0
     world, rank = _dist()
-    if ground is not None:
-        ground["world"], ground["rank"] = world, rank
-    mine = plan_frames(image_paths, output_dir, world, rank, resume, cleaned=clean is not None,
-                       clustered=cluster is not None, shaped=shapes is not None, oriented=mesh is not None,
-                       floor=floor is not None, boundary=boundary_dir)
+    mine = plan_frames(image_paths, output_dir, world, rank, resume, boundary=boundary_dir, stages=params)
     print(f"[rank {rank}/{world}] Found {len(image_paths)} images, processing {len(mine)}")
     if model is None:
         model = _model(_device(), half_precision)
@@ -443,8 +394,7 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
         nxt = 2 * decode_workers
         pending = []
         for n, k in enumerate(mine):
-            base_name = os.path.splitext(os.path.basename(image_paths[k]))[0]
-            output_path = os.path.join(output_dir, output_name(image_paths[k]))
+            base = os.path.join(output_dir, frame_file(image_paths[k], ""))
             while len(pending) >= max_inflight:
                 collect(pending.pop(0))
             try:
@@ -464,66 +414,48 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                 status = model.last_status() if hasattr(model, "last_status") else None
                 if status is not None and hasattr(status, "claim"):
                     status.claim()
-                pc = None
-                bd = None
-                gpu_img = False
+                out = {}                    # what the writer gets: {stage name: its payload}
                 if depth.is_cuda:
                     # the PNG content (colour / raw) made on the GPU, and every device->host copy,
                     # queued behind the frame on this stream; a writer thread waits on its event
                     host = _image_async(depth, colored, cmap)
-                    gpu_img = True
-                    if pointcloud:
-                        pc = _points(depth, pred["focallength_px"], image, ground, image_paths[k], clean, cluster, shapes,
-                                     mesh, floor)
-                    if boundary_dir is not None:
-                        bd = _boundary(depth, boundary_target_path(image_paths[k], boundary_dir))
+                    if list(params) == ["cloud"]:           # the base cloud alone is one step (tools swap it)
+                        out["cloud"] = _points(depth, pred["focallength_px"], image)
+                    else:
+                        frame = {"depth": depth, "f_px": pred["focallength_px"], "image": image, "path": image_paths[k],
+                                 "world": world, "rank": rank}
+                        for st in on:
+                            out[st.name] = st.queue(frame, params[st.name])
+                        if "cloud" in params:                 # the records of the cloud as the stages have left it
+                            out["cloud"] = _records(frame)
                     ev = torch.cuda.Event()
                     ev.record()
                 else:
                     host, ev = depth, None
 
-                def _finish(host=host, ev=ev, path=output_path, pc=pc, status=status, gpu_img=gpu_img,
-                            cloud=os.path.join(output_dir, cloud_name(image_paths[k], clean is not None)),
-                            cjson=os.path.join(output_dir, clusters_name(image_paths[k])),
-                            cnpy=os.path.join(output_dir, labels_name(image_paths[k])),
-                            sjson=os.path.join(output_dir, shapes_name(image_paths[k])),
-                            oply=os.path.join(output_dir, oriented_name(image_paths[k])),
-                            ojson=os.path.join(output_dir, oriented_json_name(image_paths[k])),
-                            fpng=os.path.join(output_dir, floorplan_name(image_paths[k])),
-                            fjson=os.path.join(output_dir, floorplan_json_name(image_paths[k])), bd=bd,
-                            bjson=os.path.join(output_dir, boundary_name(image_paths[k]))):
+                def _finish(host=host, ev=ev, base=base, out=out, status=status):
                     if ev is not None:
                         ev.synchronize()
                     if status is not None:
                         status.check()          # raises: this frame is dropped, nothing written
-                    if pc is not None:
-                        PC.write_ply_records(cloud, _points_host(pc))
-                        if cluster is not None:
-                            _write_clusters(pc, cluster, cjson, cnpy)
-                        if shapes is not None:
-                            _write_shapes(pc, cluster, shapes, sjson)
-                        if mesh is not None:
-                            _write_oriented(pc[-1], mesh, oply, ojson)
-                        if floor is not None:
-                            _write_floorplan(pc[-2] if mesh is not None else pc[-1], fpng, fjson)
-                    if bd is not None:
-                        scores.append(_write_boundary(bd, bjson))
-                    if gpu_img:
-                        _write_png(path, _host_image(host))
-                        return path
-                    return _encode(host.numpy(), path, colored, cmap)
+                    for st in on:
+                        if st.write is not None and out.get(st.name) is not None:
+                            st.write(base, params, out)
+                    if ev is not None:              # the PNG content was made on the GPU
+                        _write_png(base + "_depth.png", _host_image(host))
+                        return base + "_depth.png"
+                    return _encode(host.numpy(), base + "_depth.png", colored, cmap)
 
                 pending.append(enc.submit(_finish))
             except Exception as e:
                 print(f"Error generating depth map for {image_paths[k]}: {str(e)}")
                 pending.append(None)
-            print(f"[{n + 1}/{len(mine)}] Processing {base_name}")
+            print(f"[{n + 1}/{len(mine)}] Processing {frame_file(image_paths[k], '')}")
         for f in pending:
             collect(f)
-    if ground is not None and world > 1 and not ground["resolved"]:
-        _ground_plane(ground, None, None, None)      # a rank without frames still takes part in the broadcast
-    if boundary_dir is not None:
-        _report_boundary(scores, world, rank)
+    for st in on:
+        if st.end is not None:
+            st.end(params[st.name], world, rank)
     dt = time.time() - t0
     print(f"Processing complete: {successful}/{len(mine)} images successfully processed "
           f"({len(mine) / max(dt, 1e-9):.2f} frames/s on rank {rank})")
@@ -618,108 +550,146 @@ def _ground_plane(ground: dict, xyz, count, image_path):
     return model
 
 
-def _points(depth: torch.Tensor, f_px, image, ground=None, image_path=None, clean=None, cluster=None, shapes=None,
-            mesh=None, floor=None):
-    """Queue the frame's point cloud on the GPU (depth_to_3d, img_to_normalized_pointcloud.py:819-856),
-    interleaved into PLY vertex records there, and their copy into a pinned host buffer, on the
-    current stream, without a host synchronisation: the full-size record buffer + the point count
-    (the writer slices it after the frame's event and writes it as it is)."""
+def _backproject(frame: dict, p=None) -> None:
+    """Queue the frame's point cloud on the GPU (depth_to_3d, img_to_normalized_pointcloud.py:819-856) on the
+    current stream, without a host synchronisation: points, colours and the point count, all on the device."""
+    depth, image = frame["depth"], frame["image"]
     h, w = depth.shape
     rgb = image.to(depth.device, non_blocking=True) if torch.is_tensor(image) else \
         torch.from_numpy(np.ascontiguousarray(image)).to(depth.device, non_blocking=True)
-    xyz, _, cols, count = PC.depth_to_points_async(depth, f_px, w, h, rgb=rgb)
-    if ground is not None:
-        # levelled cloud (--normalize_ground): queued on the same stream, still no synchronisation
-        # once the plane is known (the first frame's fit reads back a few dozen doubles)
-        plane = _ground_plane(ground, xyz, count, image_path)
-        if plane is None:
-            raise RuntimeError("no ground plane (rank 0 could neither load nor fit one)")
-        xyz, _ = PC.normalize_to_ground(xyz, plane, count)
-        xyz, _ = PC.ground_adjust(xyz, ground["grid"], ground["pct"], count)
-        if clean is not None:
-            # cleaned cloud (--clean_pointcloud): stray points, then shadow columns; the count stays on the device
-            xyz, cols, count = PC.clean_pointcloud(xyz, cols, count, nb_points=clean["nb"], radius=clean["radius"])[:3]
-            count = count.reshape(())
-    extra = ()
-    if cluster is not None:
-        # clusters of the cleaned cloud (--cluster_pointcloud): labels, table and counts, same stream, no sync
-        labels, ncl, stats, table, order, offsets = PC.cluster_pointcloud(xyz, count, max_clusters=MAX_CLUSTERS, **cluster)
-        extra = (labels, ncl, stats, table)
-        if shapes is not None:
-            # the clusters' shapes (--fit_shapes): queued right behind the table; only the small table goes to the host
-            extra += (PC.fit_shapes(xyz, order, offsets, ncl, count, MAX_CLUSTERS, shapes["circularity_threshold"])[0],)
-            if shapes.get("l_split"):
-                # the reference's detect_and_split_l_shapes (--split_l_shapes): the rectangle list and its split, queued
-                # right behind the shapes; the small rectangle and info tables go to the host with the rest
-                rects, n_rects = PC.rectangle_list(extra[-1], ncl, MAX_CLUSTERS)
-                extra += PC.split_l_shapes(xyz, labels, rects, n_rects, count) + (n_rects,)
-    out = []
-    for t in (PC.ply_records_async(xyz, cols), count) + extra:
-        hbuf = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
-        hbuf.copy_(t, non_blocking=True)
-        out.append(hbuf)
-    if floor is not None:
-        # the occupancy floor plan of the cleaned cloud (--floor_plan): raster, morphology, regions and picture queued
-        # on the same stream.  Everything stays on the device (the grid's size is not known on the host yet); the
-        # writer makes the one read-back after the frame's event.
-        out.append(PC.floor_plan(xyz, cols, count, height_threshold=floor["height_threshold"], resolution=floor["resolution"],
-                                 min_area=floor["min_area"]))
-    if mesh is not None:
-        # the oriented point set of the cleaned cloud (--mesh_points): voxel grid, normals, orientation, and the PLY
-        # records, queued on the same stream.  Only the voxel count and the statistics are copied here; the records
-        # stay on the device (their number is not known on the host yet) and the writer fetches exactly that many.
-        op, oc, on, onrm, vst, nst = PC.oriented_points(xyz, cols, count, mesh["voxel_size"], mesh["max_nn"])
-        small = []
-        for t in (on.reshape(()), vst, nst):
-            hbuf = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
-            hbuf.copy_(t, non_blocking=True)
-            small.append(hbuf)
-        out.append({"records": PC.ply_normals_records_async(op, onrm, oc), "count": small[0], "voxel_stats": small[1],
-                    "normal_stats": small[2]})
-    return tuple(out)
+    frame["xyz"], _, frame["cols"], frame["count"] = PC.depth_to_points_async(depth, frame["f_px"], w, h, rgb=rgb)
+
+
+def _records(frame: dict) -> dict:
+    """Queue the cloud's PLY vertex records, interleaved on the GPU, and their copy into a pinned host buffer: the
+    full-size record buffer + the point count (the writer slices it after the frame's event and writes it as it is)."""
+    return {"records": _pinned(PC.ply_records_async(frame["xyz"], frame["cols"])), "count": _pinned(frame["count"])}
+
+
+def _points(depth: torch.Tensor, f_px, image) -> dict:
+    """The base cloud step, all there is to a plain --pointcloud frame: back-projection, records and count."""
+    frame = {"depth": depth, "f_px": f_px, "image": image}
+    _backproject(frame)
+    return _records(frame)
 
 
 def _points_host(pc):
     """Writer-thread side (after the frame's event): exactly the valid points' records."""
-    rec, n_host = pc[:2]
-    return rec[:int(n_host)].numpy()
+    return pc["records"][:int(pc["count"])].numpy()
 
 
-def _write_clusters(pc, cluster: dict, json_path: str, npy_path: str) -> None:
+# ---- the stages: what each queues on the frame's stream (`frame`: depth, image and the cloud as the stages so far have
+# left it, plus what one leaves on the device for a later one) and writes in the writer thread (`out`: {stage: payload}) ----
+
+def _write_cloud(base: str, params: dict, out: dict) -> None:
+    PC.write_ply_records(base + ("_clean.ply" if "clean" in params else "_points.ply"), _points_host(out["cloud"]))
+
+
+def _queue_ground(frame: dict, p: dict) -> None:
+    """The levelled cloud (--normalize_ground): no sync once the plane is known (its fit reads back a few dozen doubles)."""
+    p.update(world=frame["world"], rank=frame["rank"])
+    plane = _ground_plane(p, frame["xyz"], frame["count"], frame["path"])
+    if plane is None:
+        raise RuntimeError("no ground plane (rank 0 could neither load nor fit one)")
+    xyz, _ = PC.normalize_to_ground(frame["xyz"], plane, frame["count"])
+    frame["xyz"], _ = PC.ground_adjust(xyz, p["grid"], p["pct"], frame["count"])
+
+
+def _end_ground(p: dict, world: int, rank: int) -> None:
+    if world > 1 and not p["resolved"]:
+        p.update(world=world, rank=rank)
+        _ground_plane(p, None, None, None)      # a rank without frames still takes part in the broadcast
+
+
+def _queue_clean(frame: dict, p: dict) -> None:
+    """The cleaned cloud (--clean_pointcloud): stray points, then shadow columns; the count stays on the device."""
+    frame["xyz"], frame["cols"], count = PC.clean_pointcloud(frame["xyz"], frame["cols"], frame["count"],
+                                                             nb_points=p["nb"], radius=p["radius"])[:3]
+    frame["count"] = count.reshape(())
+
+
+def _queue_cluster(frame: dict, p: dict) -> dict:
+    """Clusters of the cleaned cloud (--cluster_pointcloud): labels, table and counts, no sync."""
+    labels, ncl, stats, table, order, offsets = PC.cluster_pointcloud(frame["xyz"], frame["count"], max_clusters=MAX_CLUSTERS, **p)
+    frame.update(labels=labels, n_clusters=ncl, order=order, offsets=offsets)
+    return {"labels": _pinned(labels), "n_clusters": _pinned(ncl), "stats": _pinned(stats), "table": _pinned(table)}
+
+
+def _write_clusters(base: str, params: dict, out: dict) -> None:
     """Writer-thread side: `{base}_labels.npy` (the live rows' labels) and `{base}_clusters.json`."""
-    import json
-
-    n, (labels, ncl, stats, table) = int(pc[1]), pc[2:6]
-    np.save(npy_path, labels[:n].numpy())
-    k = min(int(ncl), MAX_CLUSTERS)
-    with open(json_path, "w") as f:
-        params = {key: (None if isinstance(v, float) and v != v else v) for key, v in cluster.items()}   # NaN height
-        json.dump(PC.cluster_summary(table[:k].numpy(), stats.numpy(), params), f, indent=1)
+    c = out["cluster"]
+    np.save(base + "_labels.npy", c["labels"][:int(out["cloud"]["count"])].numpy())
+    k = min(int(c["n_clusters"]), MAX_CLUSTERS)
+    with open(base + "_clusters.json", "w") as f:
+        p = {key: (None if isinstance(v, float) and v != v else v) for key, v in params["cluster"].items()}   # NaN height
+        json.dump(PC.cluster_summary(c["table"][:k].numpy(), c["stats"].numpy(), p), f, indent=1)
 
 
-def _write_shapes(pc, cluster: dict, shapes: dict, json_path: str) -> None:
+def _queue_shapes(frame: dict, p: dict) -> dict:
+    """The clusters' shapes (--fit_shapes), right behind the table, and with --split_l_shapes the reference's
+    detect_and_split_l_shapes behind them (rectangle list, split); only the small tables go to the host."""
+    table = PC.fit_shapes(frame["xyz"], frame["order"], frame["offsets"], frame["n_clusters"], frame["count"], MAX_CLUSTERS,
+                          p["circularity_threshold"])[0]
+    payload = {"table": _pinned(table)}
+    if p.get("l_split"):
+        rects, n_rects = PC.rectangle_list(table, frame["n_clusters"], MAX_CLUSTERS)
+        rows, n_out, info = PC.split_l_shapes(frame["xyz"], frame["labels"], rects, n_rects, frame["count"])
+        payload["l_split"] = {"rows": _pinned(rows), "n_out": _pinned(n_out), "info": _pinned(info), "n_rects": _pinned(n_rects)}
+    return payload
+
+
+def _write_shapes(base: str, params: dict, out: dict) -> None:
     """Writer-thread side: `{base}_shapes.json` and `{base}_shapes.txt`."""
-    import json
-
-    k = min(int(pc[3]), MAX_CLUSTERS)
-    params = {key: (None if isinstance(v, float) and v != v else v) for key, v in {**cluster, **shapes}.items()
-              if key != "l_split"}
-    if shapes.get("l_split"):
-        rows, n_out, info, n_rects = pc[7:11]
-        summary = PC.shape_summary(pc[6][:k].numpy(), params, rows[:int(n_out[0])].numpy(), info[:int(n_rects)].numpy())
-        summary["l_overflow"] = bool(n_out[1])
+    s, split = out["shapes"], out["shapes"].get("l_split")
+    table = s["table"][:min(int(out["cluster"]["n_clusters"]), MAX_CLUSTERS)].numpy()
+    p = {key: (None if isinstance(v, float) and v != v else v) for key, v in {**params["cluster"], **params["shapes"]}.items()
+         if key != "l_split"}
+    if split is not None:
+        summary = PC.shape_summary(table, p, split["rows"][:int(split["n_out"][0])].numpy(),
+                                   split["info"][:int(split["n_rects"])].numpy())
+        summary["l_overflow"] = bool(split["n_out"][1])
     else:
-        summary = PC.shape_summary(pc[6][:k].numpy(), params)
-    with open(json_path, "w") as f:
+        summary = PC.shape_summary(table, p)
+    with open(base + "_shapes.json", "w") as f:
         json.dump(summary, f, indent=1)
-    PC.export_shape_text(summary, os.path.splitext(json_path)[0] + ".txt")
+    PC.export_shape_text(summary, base + "_shapes.txt")
 
 
-def _write_oriented(m: dict, mesh: dict, ply_path: str, json_path: str) -> None:
+def _queue_floor(frame: dict, p: dict) -> dict:
+    """The occupancy floor plan of the cleaned cloud (--floor_plan): raster, morphology, regions and picture, all left
+    on the device (the grid's size is not known on the host yet); the writer makes the one read-back after the event."""
+    return PC.floor_plan(frame["xyz"], frame["cols"], frame["count"], height_threshold=p["height_threshold"],
+                         resolution=p["resolution"], min_area=p["min_area"])
+
+
+def _write_floorplan(base: str, params: dict, out: dict) -> None:
+    """Writer-thread side (after the frame's event, so the plan is complete): the one read-back on a stream of this
+    thread's own, then `{base}_floorplan.png` (PIL) and `{base}_floorplan.json`."""
+    from PIL import Image
+
+    plan = out["floor"]
+    side = torch.cuda.Stream(plan["image"].device)
+    with torch.cuda.stream(side):
+        summary = PC.floor_plan_summary(plan)
+    img = summary.pop("image")
+    # no participants, or a grid past the capacity: a 1 x 1 white picture
+    (Image.fromarray(img, "RGB") if img.size else Image.new("RGB", (1, 1), (255, 255, 255))).save(base + "_floorplan.png")
+    with open(base + "_floorplan.json", "w") as f:
+        json.dump(summary, f, indent=1)
+
+
+def _queue_mesh(frame: dict, p: dict) -> dict:
+    """The oriented point set of the cleaned cloud (--mesh_points): voxel grid, normals, orientation, PLY records.  Only
+    the voxel count and the statistics are copied here; the records stay on the device and the writer fetches `count`."""
+    op, oc, on, onrm, vst, nst = PC.oriented_points(frame["xyz"], frame["cols"], frame["count"], p["voxel_size"], p["max_nn"])
+    return {"count": _pinned(on.reshape(())), "voxel_stats": _pinned(vst), "normal_stats": _pinned(nst),
+            "records": PC.ply_normals_records_async(op, onrm, oc)}
+
+
+def _write_oriented(base: str, params: dict, out: dict) -> None:
     """Writer-thread side (after the frame's event, so the records are complete): fetch the first `count` records
     on a stream of this thread's own, then `{base}_oriented.ply` and `{base}_oriented.json`."""
-    import json
-
+    m, mesh = out["mesh"], params["mesh"]
     rec = m["records"]
     n = max(0, min(int(m["count"]), rec.shape[0]))
     side = torch.cuda.Stream(rec.device)
@@ -727,22 +697,22 @@ def _write_oriented(m: dict, mesh: dict, ply_path: str, json_path: str) -> None:
         host = torch.empty((n, rec.shape[1]), dtype=rec.dtype, pin_memory=True)
         host.copy_(rec[:n], non_blocking=True)
     side.synchronize()
-    PC.write_ply_normals_records(ply_path, host.numpy())
+    PC.write_ply_normals_records(base + "_oriented.ply", host.numpy())
     summary = {"parameters": {"voxel_size": mesh["voxel_size"], "radius": 2.0 * mesh["voxel_size"], "max_nn": mesh["max_nn"],
                               "camera_location": [0.0, 0.0, 0.0]},
                "points": n,
                "voxel_stats": {k: float(v) for k, v in zip(PC.VOXEL_STATS, m["voxel_stats"].numpy())},
                "normal_stats": {k: float(v) for k, v in zip(PC.NORMAL_STATS, m["normal_stats"].numpy())}}
-    with open(json_path, "w") as f:
+    with open(base + "_oriented.json", "w") as f:
         json.dump(summary, f, indent=1)
 
 
-def _boundary(depth: torch.Tensor, target_path: str):
-    """Queue the frame's boundary counts against its target on the current stream (depth_pro.eval.boundary_metrics:
-    the depth is still on the device) and their copy into pinned host memory.  None, with a line of report, when the
-    target is missing or cannot be used."""
+def _boundary(frame: dict, p: dict):
+    """Queue the frame's boundary counts against its target (depth_pro.eval.boundary_metrics: the depth is still on the
+    device) and their pinned host copy.  None, with a line of report, when the target is missing or cannot be used."""
     from depth_pro.eval import boundary_metrics as BM
 
+    depth, target_path = frame["depth"], boundary_target_path(frame["path"], p["dir"])
     if not os.path.exists(target_path):
         print(f"No boundary target {target_path}: frame not scored")
         return None
@@ -763,29 +733,26 @@ def _boundary(depth: torch.Tensor, target_path: str):
     except Exception as e:
         print(f"Boundary target {target_path} not used: {e}")
         return None
-    host = torch.empty(counts.shape, dtype=counts.dtype, pin_memory=True)
-    host.copy_(counts, non_blocking=True)
-    return {"kind": kind, "name": name, "counts": host, "thresholds": thresholds, "shape": tuple(depth.shape)}
+    return {"kind": kind, "name": name, "counts": _pinned(counts), "thresholds": thresholds, "shape": tuple(depth.shape)}
 
 
-def _write_boundary(bd: dict, json_path: str) -> float:
-    """Writer-thread side (after the frame's event): the score from the counts, `{base}_boundary.json`."""
-    import json
-
+def _write_boundary(base: str, params: dict, out: dict) -> None:
+    """Writer-thread side: the score from the counts, `{base}_boundary.json`; the run keeps the score for its mean."""
     from depth_pro.eval import boundary_metrics as BM
 
+    bd = out["boundary"]
     counts = bd["counts"].numpy().tolist()
     score = float(BM.weighted_score(counts, bd["thresholds"], bd["kind"]))
-    with open(json_path, "w") as f:
+    with open(base + "_boundary.json", "w") as f:
         json.dump({"kind": bd["name"], "metric": "SI_boundary_F1" if bd["kind"] == BM.DP_BOUNDARY_DEPTH else "SI_boundary_Recall",
                    "score": score, "thresholds": [float(t) for t in bd["thresholds"]], "directions": list(BM.DIRECTIONS),
                    "count_names": list(BM.COUNTS), "counts": counts, "H": bd["shape"][0], "W": bd["shape"][1]}, f, indent=1)
-    return score
+    params["boundary"]["scores"].append(score)
 
 
-def _report_boundary(scores, world: int, rank: int) -> None:
+def _report_boundary(p: dict, world: int, rank: int) -> None:
     """Rank 0 prints the mean boundary score over the frames scored (one all-reduce of sum and count with several ranks)."""
-    total, n = float(sum(scores)), len(scores)
+    total, n = float(sum(p["scores"])), len(p["scores"])
     if world > 1:
         box = torch.tensor([total, float(n)], dtype=torch.float64, device=_device() if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(box)
@@ -794,23 +761,75 @@ def _report_boundary(scores, world: int, rank: int) -> None:
         print(f"mean boundary score over {n} frames: {total / n:.6f}" if n else "no frame had a usable boundary target")
 
 
-def _write_floorplan(plan: dict, png_path: str, json_path: str) -> None:
-    """Writer-thread side (after the frame's event, so the plan is complete): the one read-back on a stream of this
-    thread's own, then `{base}_floorplan.png` (PIL) and `{base}_floorplan.json`."""
-    import json
+# ---- each stage's parameter dict from the loop's options `o`, checked first ----
 
-    from PIL import Image
+def _ground_params(o: dict) -> dict:
+    check_grid_size(o["grid_size"])
+    return {"model": None, "dir": o["ground_params_dir"] or o.get("output_dir"), "grid": int(o["grid_size"]),
+            "pct": o["ground_percentile"], "rot": o["rotation_offset"], "resolved": False}
 
-    side = torch.cuda.Stream(plan["image"].device)
-    with torch.cuda.stream(side):
-        summary = PC.floor_plan_summary(plan)
-    img = summary.pop("image")
-    if img.size:
-        Image.fromarray(img, "RGB").save(png_path)
-    else:                                        # no participants, or a grid past the capacity: a 1 x 1 white picture
-        Image.new("RGB", (1, 1), (255, 255, 255)).save(png_path)
-    with open(json_path, "w") as f:
-        json.dump(summary, f, indent=1)
+
+def _clean_params(o: dict) -> dict:
+    check_stray(o["stray_radius"], o["stray_neighbors"])
+    return {"radius": float(o["stray_radius"]), "nb": int(o["stray_neighbors"])}
+
+
+def _cluster_params(o: dict) -> dict:
+    check_cluster(o["cluster_eps"], o["cluster_min_samples"], o["cluster_max_points"])
+    return {"eps": float(o["cluster_eps"]), "min_samples": int(o["cluster_min_samples"]),
+            "height_threshold": float(o["cluster_height"]), "max_points": int(o["cluster_max_points"])}
+
+
+def _shapes_params(o: dict) -> dict:
+    check_circularity(o["circularity_threshold"])
+    return {"circularity_threshold": float(o["circularity_threshold"]), **({"l_split": True} if o["split_l_shapes"] else {})}
+
+
+def _floor_params(o: dict) -> dict:
+    check_floor(o["floor_resolution"], o["floor_height"], o["floor_min_area"])
+    return {"resolution": float(o["floor_resolution"]), "height_threshold": float(o["floor_height"]),
+            "min_area": float(o["floor_min_area"])}
+
+
+def _mesh_params(o: dict) -> dict:
+    check_mesh(o["voxel_size"], o["normals_max_nn"])
+    return {"voxel_size": float(o["voxel_size"]), "max_nn": int(o["normals_max_nn"])}
+
+
+def _boundary_params(o: dict) -> dict:
+    check_boundary_dir(o["boundary_dir"])
+    return {"dir": o["boundary_dir"], "scores": []}
+
+
+class Stage(NamedTuple):
+    """One stage of the frame loop, described once."""
+    name: str
+    implies: Optional[str]              # the stage that has to be on for this one
+    on: Callable[[dict], bool]          # the loop's options -> does the caller ask for it
+    params: Callable[[dict], dict]      # the loop's options -> its parameter dict, checked (ValueError)
+    suffixes: Tuple[str, ...]           # --resume: a finished frame has `{base}{suffix}` for each
+    queue: Callable                     # (frame, its parameters) -> payload: its GPU work, on the current stream
+    write: Optional[Callable]           # (base path, {stage: parameters}, {stage: payload}): its files, writer thread
+    end: Optional[Callable] = None      # (its parameters, world, rank): after the last frame
+
+
+# in the order they are queued on a frame's stream; a stage stands behind the one it implies
+STAGES = (
+    Stage("cloud", None, lambda o: o["pointcloud"], lambda o: {}, (), _backproject, _write_cloud),
+    Stage("ground", "cloud", lambda o: o["normalize_ground"], _ground_params, (), _queue_ground, None, _end_ground),
+    Stage("clean", "ground", lambda o: o["clean_pointcloud"], _clean_params, ("_clean.ply",), _queue_clean, None),
+    Stage("cluster", "clean", lambda o: o["cluster_pointcloud"], _cluster_params, ("_clusters.json",),
+          _queue_cluster, _write_clusters),
+    Stage("shapes", "cluster", lambda o: o["fit_shapes"] or o["split_l_shapes"], _shapes_params, ("_shapes.json",),
+          _queue_shapes, _write_shapes),
+    Stage("floor", "clean", lambda o: o["floor_plan"], _floor_params, ("_floorplan.png", "_floorplan.json"),
+          _queue_floor, _write_floorplan),
+    Stage("mesh", "clean", lambda o: o["mesh_points"], _mesh_params, ("_oriented.ply", "_oriented.json"),
+          _queue_mesh, _write_oriented),
+    Stage("boundary", None, lambda o: o["boundary_dir"] is not None, _boundary_params, ("_boundary.json",),
+          _boundary, _write_boundary, _report_boundary),
+)
+_DEFAULTS = {k: p.default for k, p in inspect.signature(batch_generate_depth_maps).parameters.items() if p.default is not p.empty}
 
 
 def main():
@@ -889,39 +908,19 @@ def main():
                         choices=["turbo", "viridis", "plasma", "inferno", "magma", "cividis", "jet"],
                         help="Colormap for depth visualization")
     args = parser.parse_args()
-    if not 1 <= args.grid_size <= MAX_GRID_SIZE:
-        parser.error(f"--grid_size must be in [1, {MAX_GRID_SIZE}] (got {args.grid_size})")
-    if not 0 <= args.ground_percentile <= 100:
-        parser.error("--ground_percentile must be in [0, 100]")
+    kw = vars(args)
+    kw.update(colored=not kw.pop("raw"), cmap=kw.pop("colormap"), rotation_offset=[kw.pop(f"rot_{a}") for a in "xyz"])
     try:
-        check_stray(args.stray_radius, args.stray_neighbors)
+        check_grid_size(args.grid_size)
+        if not 0 <= args.ground_percentile <= 100:
+            raise ValueError("--ground_percentile must be in [0, 100]")
+        check_stray(args.stray_radius, args.stray_neighbors)         # these, whether their stage is on or not
         check_cluster(args.cluster_eps, args.cluster_min_samples, args.cluster_max_points)
         check_circularity(args.circularity_threshold)
-        if args.mesh_points:
-            check_mesh(args.voxel_size, args.normals_max_nn)
-        if args.floor_plan:
-            check_floor(args.floor_resolution, args.floor_height, args.floor_min_area)
-        if args.boundary_dir is not None:
-            check_boundary_dir(args.boundary_dir)
+        resolve_stages(**kw)                                         # and every stage that is on
     except ValueError as e:
         parser.error(str(e))
-    batch_generate_depth_maps(input_dir=args.input_dir, output_dir=args.output_dir, pattern=args.pattern,
-                              downscale_factor=args.downscale_factor, half_precision=args.half_precision,
-                              colored=not args.raw, cmap=args.colormap, pointcloud=args.pointcloud,
-                              resume=args.resume, normalize_ground=args.normalize_ground,
-                              ground_params_dir=args.ground_params_dir, grid_size=args.grid_size,
-                              ground_percentile=args.ground_percentile,
-                              rotation_offset=[args.rot_x, args.rot_y, args.rot_z],
-                              clean_pointcloud=args.clean_pointcloud, stray_radius=args.stray_radius,
-                              stray_neighbors=args.stray_neighbors, cluster_pointcloud=args.cluster_pointcloud,
-                              cluster_eps=args.cluster_eps, cluster_min_samples=args.cluster_min_samples,
-                              cluster_height=args.cluster_height, cluster_max_points=args.cluster_max_points,
-                              fit_shapes=args.fit_shapes, split_l_shapes=args.split_l_shapes,
-                              circularity_threshold=args.circularity_threshold,
-                              mesh_points=args.mesh_points, voxel_size=args.voxel_size, normals_max_nn=args.normals_max_nn,
-                              floor_plan=args.floor_plan, floor_resolution=args.floor_resolution,
-                              floor_height=args.floor_height, floor_min_area=args.floor_min_area,
-                              boundary_dir=args.boundary_dir)
+    batch_generate_depth_maps(**kw)
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()

@@ -44,6 +44,8 @@ def main():
                     help="cluster the cleaned clouds (--cluster_pointcloud of the loop; implies --clean-pointcloud)")
     ap.add_argument("--fit-shapes", action="store_true",
                     help="fit the clusters' shapes (--fit_shapes of the loop; implies --cluster-pointcloud)")
+    ap.add_argument("--split-l-shapes", action="store_true",
+                    help="split L-shaped rectangles (--split_l_shapes of the loop; implies --fit-shapes)")
     ap.add_argument("--mesh-points", action="store_true",
                     help="write the oriented mesh points (--mesh_points of the loop; implies --clean-pointcloud)")
     ap.add_argument("--floor-plan", action="store_true",
@@ -98,12 +100,7 @@ def main():
             rgb = image.to(depth.device, non_blocking=True) if torch.is_tensor(image) else \
                 torch.from_numpy(np.ascontiguousarray(image)).to(depth.device, non_blocking=True)
             xyz, _, cols, count = PC.depth_to_points_async(depth, f_px, w, h, rgb=rgb)
-            out = []
-            for t in (xyz, cols, count):
-                hb = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
-                hb.copy_(t, non_blocking=True)
-                out.append(hb)
-            return tuple(out)
+            return tuple(G._pinned(t) for t in (xyz, cols, count))
 
         def records_on_host(pc):
             xyz, cols, cnt = pc
@@ -134,27 +131,11 @@ def main():
     m, transform = model
     torch.cuda.synchronize()
     t_setup = time.time() - t
-    if args.fit_shapes:
-        args.cluster_pointcloud = True
-    if args.cluster_pointcloud or args.mesh_points or args.floor_plan:
-        args.clean_pointcloud = True
-    if args.clean_pointcloud:
-        args.normalize_ground = True
-    if args.normalize_ground:
-        args.pointcloud = True
-    kw = dict(colored=not args.raw, pointcloud=args.pointcloud, model=model)
-    if args.normalize_ground:
-        kw["normalize_ground"] = True
-    if args.clean_pointcloud:
-        kw["clean_pointcloud"] = True
-    if args.cluster_pointcloud:
-        kw["cluster_pointcloud"] = True
-    if args.fit_shapes:
-        kw["fit_shapes"] = True
-    if args.mesh_points:
-        kw["mesh_points"] = True
-    if args.floor_plan:
-        kw["floor_plan"] = True
+    # the stage flags go to the loop as they are: it implies the rest (G.resolve_stages)
+    flags = {k: getattr(args, k) for k in ("pointcloud", "normalize_ground", "clean_pointcloud", "cluster_pointcloud",
+                                           "fit_shapes", "split_l_shapes", "mesh_points", "floor_plan")}
+    stages = list(G.resolve_stages(**flags))
+    kw = dict(colored=not args.raw, model=model, **flags)
     if args.workers:
         kw.update(decode_workers=args.workers, encode_workers=args.workers)
     import inspect
@@ -223,7 +204,7 @@ def main():
                     enumerate(hosts)))
     t_enc = (time.time() - t) / len(hosts)
     t_ply = None
-    if args.pointcloud:
+    if "cloud" in stages:
         img_dev = (imgs[0] if torch.is_tensor(imgs[0]) else torch.from_numpy(imgs[0])).to(dev)
         f = m.infer(transform(imgs[0]))["focallength_px"]
         xyz, _, cols, count = PC.depth_to_points_async(depths[0], f, W, H, rgb=img_dev)
@@ -239,10 +220,7 @@ def main():
         t_ply = time.time() - t
     out = {
         "what": "generate_depth_maps.batch_generate_depth_maps end to end, 1 GPU",
-        "frames": args.frames, "size": [W, H], "pointcloud": args.pointcloud, "normalize_ground": args.normalize_ground,
-        "clean_pointcloud": args.clean_pointcloud, "cluster_pointcloud": args.cluster_pointcloud,
-        "fit_shapes": args.fit_shapes, "mesh_points": args.mesh_points, "floor_plan": args.floor_plan,
-        "raw": args.raw,
+        "frames": args.frames, "size": [W, H], "stages": stages, "l_split": args.split_l_shapes, "raw": args.raw,
         "ply_records": "host (numpy)" if args.ply_host else "GPU",
         "png_writer": "bytes copies" if args.png_copy else "zero-copy parts",
         "switch_ms": args.switch_ms,

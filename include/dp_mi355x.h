@@ -340,7 +340,8 @@ int dp_attention_log2q(const void* qkv, void* out, int32_t batch, int32_t seq, i
 
 /*
  * dp_normalize_u8: uint8 HWC image -> (x/255 - 0.5)/0.5 planar CHW (fp32 or 16-bit).
- * Replaces the transform Compose (depth_pro.py:125-132) with the u8 upload + GPU normalize.
+ * The value is computed in fp32 (IEEE division); a 16-bit output is that fp32 value rounded to
+ * nearest even.  Replaces the transform Compose (depth_pro.py:125-132) with the u8 upload + GPU normalize.
  */
 int dp_normalize_u8(const uint8_t* img_hwc, int32_t H, int32_t W, void* out_chw, int32_t out_dtype,
                     dp_stream_t stream);
@@ -357,6 +358,9 @@ int dp_resize_bilinear(const void* src, int32_t src_dtype, int32_t C, int32_t H,
  * dp_resize: dp_resize_bilinear with the F.interpolate mode DepthPro.infer passes through
  * (`interpolation_mode`, depth_pro.py:243-279): DP_INTERP_BILINEAR, or DP_INTERP_BICUBIC
  * (upsample_bicubic2d, align_corners=False, A = -0.75, border taps clamped).
+ * Same size in and out (H == OH and W == OW) is a copy in either mode, at any element alignment
+ * of src and dst: every value, a NaN or an infinity included, arrives unchanged (a 16-bit source
+ * upcast exactly) and touches no neighbour.
  */
 enum { DP_INTERP_BILINEAR = 0, DP_INTERP_BICUBIC = 1 };
 int dp_resize(const void* src, int32_t src_dtype, int32_t C, int32_t H, int32_t W, float* dst,
@@ -392,6 +396,10 @@ int dp_merge_windows(const void* src, int32_t src_dtype, int64_t ld_src, int32_t
  * steps x steps grid (w = row * steps + column); the other pixels of dst are not written.
  * For a patch encoder run as several independent window groups (each merges its own share
  * of a hooked block's output before it moves on).
+ * Both calls reject, before any launch: ld_src % 8 != 0, steps > 1 with 24 - 2 * padding <= 0,
+ * w_lo >= w_hi, w_lo < 0 or w_hi > steps * steps (DP_ERR_SHAPE); a 16-bit source of the other
+ * 16-bit kind than `dtype`, or a `dtype` that is not 16-bit (DP_ERR_DTYPE).  steps == 1 ignores
+ * `padding`.
  */
 int dp_merge_windows_range(const void* src, int32_t src_dtype, int64_t ld_src, int32_t first_window,
                            int32_t steps, int32_t padding, int32_t w_lo, int32_t w_hi, void* dst,

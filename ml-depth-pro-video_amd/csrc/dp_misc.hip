@@ -263,12 +263,13 @@ __global__ void resize_kernel(const void* __restrict__ src, int C, int H, int W,
 }
 
 // Same size in and out: F.interpolate's upsample kernels copy the input then (PyTorch's
-// input == output size fast path), so this one does too -- 16 B per lane for fp32 planes
+// input == output size fast path), so this one does too -- 16 B per lane for fp32 planes whose
+// two bases are 16-B aligned (`vec`), element by element otherwise
 template <int SRC>
-__global__ void resize_copy_kernel(const void* __restrict__ src, float* __restrict__ dst, long long total) {
+__global__ void resize_copy_kernel(const void* __restrict__ src, float* __restrict__ dst, long long total, int vec) {
   const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   if (i >= total) return;
-  if (SRC == DP_F32 && i + 4 <= total) {
+  if (SRC == DP_F32 && vec && i + 4 <= total) {
     *(float4*)(dst + i) = *(const float4*)((const float*)src + i);
     return;
   }
@@ -634,11 +635,12 @@ extern "C" int dp_resize(const void* src, int32_t src_dtype, int32_t C, int32_t 
   const long long total = (long long)C * OH * OW;
   const float sh = (float)H / (float)OH, sw = (float)W / (float)OW;
   hipStream_t s = (hipStream_t)stream;
-  if (H == OH && W == OW && ((uintptr_t)src | (uintptr_t)dst) % 16 == 0) {   // (the 1536^2 infer prologue)
+  if (H == OH && W == OW) {   // a copy at any element alignment (the 1536^2 infer prologue)
+    const int vec = ((uintptr_t)src | (uintptr_t)dst) % 16 == 0;
     dim3 gc(blocks_for((total + 3) / 4, 256));
-    if (src_dtype == DP_F32) hipLaunchKernelGGL(resize_copy_kernel<DP_F32>, gc, dim3(256), 0, s, src, dst, total);
-    else if (src_dtype == DP_BF16) hipLaunchKernelGGL(resize_copy_kernel<DP_BF16>, gc, dim3(256), 0, s, src, dst, total);
-    else if (src_dtype == DP_F16) hipLaunchKernelGGL(resize_copy_kernel<DP_F16>, gc, dim3(256), 0, s, src, dst, total);
+    if (src_dtype == DP_F32) hipLaunchKernelGGL(resize_copy_kernel<DP_F32>, gc, dim3(256), 0, s, src, dst, total, vec);
+    else if (src_dtype == DP_BF16) hipLaunchKernelGGL(resize_copy_kernel<DP_BF16>, gc, dim3(256), 0, s, src, dst, total, vec);
+    else if (src_dtype == DP_F16) hipLaunchKernelGGL(resize_copy_kernel<DP_F16>, gc, dim3(256), 0, s, src, dst, total, vec);
     else return DP_ERR_DTYPE;
     DP_CHECK_LAUNCH();
     return 0;

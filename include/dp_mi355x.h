@@ -151,13 +151,41 @@ typedef struct dp_gemm_args {
    *  producer on a SPLIT residual (ABI 12, ln_xl != NULL): the residual stream is held as a 16-bit
    *    high part (ln_xb_out, dtype, [M][ldc]) and an int8 low part (ln_xl, [M][ldc] bytes), read and
    *    updated in place:  x = hi + q * 2^(e - S)  with e the frexp exponent of hi (hi = m 2^e,
-   *    m in [0.5, 1)), S = 16 (bf16) / 19 (f16), i.e. q counts steps of ulp(hi) / 256;
-   *    x' = v + x;  hi' = x' rounded to 16 bits;  q' = clamp(rint((x' - hi') 2^(S - e')), -128, 127)
+   *    m in [0.5, 1)), S = 16 (bf16) / 19 (f16), i.e. q counts steps of ulp(hi) / 256 for a
+   *    normal hi;
+   *    x' = v + x, v = (acc + bias[n]) * gamma[n];  hi' = x' rounded to 16 bits (nearest even);
+   *    q' = clamp(rint((x' - hi') 2^(S - e')), -128, 127), e' the frexp exponent of hi': half a
+   *    step of error, 1.5 steps at the one clamped value (the exact tie x' - hi' = +ulp(hi') / 2
+   *    gives 128).  Edges: hi = 0 has e = 0 and q = 0.  A subnormal f16 hi (|hi| < 2^-14) keeps
+   *    its frexp exponent, so its step 2^(e - 19) is finer than ulp(hi) / 256 = 2^-32 and
+   *    |x - hi| <= 2^-25 can be up to 2^(-6 - e) >= 256 steps: q then saturates at -128 / 127
+   *    and the error is bounded by the 16-bit rounding's 2^-25 instead of half a step.  An f16
+   *    hi' of +-inf (|x'| >= 65520) is stored as such with q' = -128 / 127, and the element
+   *    stays +-inf from then on (the fp32 C, when given, still receives the finite x')
    *    (~16 significant bits: the patch encoder's error vs fp32 moves 2.3788e-3 -> 2.3809e-3,
    *    tools/hilo_emul.py); ln_part_out as above or NULL; C (fp32, [M][ldc]) is not read: NULL, or
-   *    written with x' (for a reader of the fp32 rows); accumulate = 1, act none, N % 128 == 0,
+   *    written with x' (for a reader of the fp32 rows); accumulate = 1, act none, ldc % 8 == 0,
    *    M * ldc * 4 < 2^32 - 256.  6 instead of 10 bytes of HBM traffic per element in a residual
-   *    GEMM's epilogue. */
+   *    GEMM's epilogue.
+   *  What a launch with an ln_* field must meet (DP_ERR_ARG otherwise; checked right after the
+   *  general checks -- where accumulate with a 16-bit C is DP_ERR_DTYPE -- and before the 8-column
+   *  rules, which apply to every ln_* launch whatever the hint: ldc % 8 == 0 for a 16-bit C):
+   *    every ln_* launch: what DP_TILE_8PH_320x256 takes (dense A, no relu_a, N % 256 == 0,
+   *      DP_STORE_ROWS, no R1 / R2 / pos / row groups / head, M * lda and N * ldb below 2^31);
+   *      a tile hint other than DP_TILE_AUTO and DP_TILE_8PH_320x256 is DP_ERR_ARG, except
+   *      DP_TILE_P8PH_256x256 on a consumer; no producer field together with a consumer field;
+   *    fp32 producer (ln_xl NULL): ln_part_out and ln_xb_out both, C fp32 and accumulated into,
+   *      act none;
+   *    split producer: ln_xb_out, accumulate = 1 and c_dtype DP_F32 (also when C is NULL), act
+   *      none, ldc % 8 == 0, the extent limit above;
+   *    consumer: ln_colsum and exactly one of ln_part_in / ln_rs_in, K == 1024, ln_eps > 0 (0,
+   *      negative and NaN are refused), act none or GELU, gamma NULL, a 16-bit C, no accumulate.
+   *      It runs on the 8-phase 320 x 256 engine, or on the persistent 8-phase engine where the
+   *      planner or a DP_TILE_P8PH_256x256 hint puts it and its merged row statistics have a
+   *      place: ln_rs_in, or ln_part_in with a workspace and M <= 32768.  An ln_part_in consumer
+   *      hinted DP_TILE_P8PH_256x256 without those runs on the 320 x 256 engine -- the one hint
+   *      that is rerouted rather than refused (both engines compute the same contract); a
+   *      problem the persistent engine does not take at all stays DP_ERR_ARG under the hint. */
   float* ln_part_out;
   void* ln_xb_out;
   const float* ln_part_in;
@@ -170,7 +198,12 @@ typedef struct dp_gemm_args {
    * rows' 8 chunk statistics into ln_rs_out[m] = (rstd, -rstd * mean) (eps ln_eps; the arithmetic
    * of the pre-pass, bit for bit); a consumer on the persistent 8-phase engine takes ln_rs_in =
    * that array instead of ln_part_in (no pre-pass launch, no workspace needed).  ln_rs_in holds
-   * M rounded up to an even number of rows (its reads go in row pairs). */
+   * M rounded up to an even number of rows (its reads go in row pairs; the pad row's values are
+   * never used).  ln_rs_out needs (DP_ERR_ARG): ln_xl, ln_part_out, N == 1024, ln_eps > 0, a
+   * workspace of dp_gemm_workspace_size() bytes, and ceil(M / 320) <= 511, i.e. M <= 163520 (one
+   * counter per row tile, workspace words 512 .. 1022; each is zero again when the launch ends).
+   * ln_rs_in runs only on the persistent engine: DP_TILE_AUTO and DP_TILE_P8PH_256x256 both mean
+   * that engine, at every M; any other hint is DP_ERR_ARG. */
   float* ln_rs_out;
   const float* ln_rs_in;
 } dp_gemm_args;
@@ -295,13 +328,15 @@ int dp_layernorm(const float* x, int64_t ldx, const float* w, const float* b, vo
 
 /*
  * dp_layernorm_stats: the input side of a folded LayerNorm (dp_gemm_args.ln_*): for the rows of
- * fp32 x [rows][cols] (cols % 128 == 0, <= 2048) write x in 16 bits (xb [rows][ldxb], dtype) and
+ * fp32 x [rows][cols] (cols: 512, 1024 or 2048) write x in 16 bits (xb [rows][ldxb], dtype) and
  * part fp32 [rows][cols/128][2] = (mean, M2) of each 128-column chunk -- what the residual GEMMs'
  * producer epilogue writes, for the rows no GEMM produced (the patch embed + cls rows that enter
  * ViT block 0).  xl (ABI 12; NULL: none): the int8 low part of the split residual ([rows][ldxb]
  * bytes, the encoding of dp_gemm_args.ln_xl), so that (xb, xl) is the stream a split-residual
  * producer reads.  ldx % 4 == 0, ldxb % 8 == 0; x and xb must be 16-B aligned, xl and part 8-B
- * aligned (DP_ERR_ALIGN).
+ * aligned (DP_ERR_ALIGN).  Checks, in this order: x, xb or part NULL (DP_ERR_ARG); rows <= 0
+ * (DP_ERR_SHAPE); ldx, ldxb, then the pointers (DP_ERR_ALIGN); cols not one of the three
+ * (DP_ERR_SHAPE); dtype not DP_BF16 / DP_F16 (DP_ERR_DTYPE).
  */
 int dp_layernorm_stats(const float* x, int64_t ldx, int32_t rows, int32_t cols, void* xb, int64_t ldxb,
                        void* xl, float* part, int32_t dtype, dp_stream_t stream);

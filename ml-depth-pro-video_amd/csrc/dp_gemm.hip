@@ -114,18 +114,18 @@ int gemm_plan(const dp_gemm_args* a, GemmP& p, int& tile) {
       return DP_ERR_SHAPE;
   }
   // folded LayerNorm (ln_*): the 8-phase 320 x 256 engine only, producer = the fp32 residual
-  // accumulate without activation (N % 128 == 0), consumer = 16-bit C over K = 1024 rows whose
-  // gamma is folded into B / bias
+  // accumulate without activation (N % 256 == 0: the engine's tiles), consumer = 16-bit C over
+  // K = 1024 rows whose gamma is folded into B / bias
   const bool lnp = a->ln_part_out || a->ln_xb_out || a->ln_xl || a->ln_rs_out,
              lnc = a->ln_part_in || a->ln_colsum || a->ln_rs_in;
   if (lnp && lnc) return DP_ERR_ARG;
   if (lnp && !a->ln_xl && (!a->ln_part_out || !a->ln_xb_out || !a->accumulate || !a->C || a->c_dtype != DP_F32 ||
-                           a->act != DP_ACT_NONE || a->N % 128 != 0))
+                           a->act != DP_ACT_NONE || a->N % 256 != 0))
     return DP_ERR_ARG;
   // the split residual (ABI 12): x = ln_xb_out + ln_xl, both 16-bit [M][ldc], updated in place; part and
   // an fp32 copy in C optional; every byte extent below the buffer-store bound
   if (a->ln_xl && (!a->ln_xb_out || !a->accumulate || a->c_dtype != DP_F32 || a->act != DP_ACT_NONE ||
-                   a->N % 128 != 0 || a->ldc % 8 != 0 || (long long)a->M * a->ldc * 4 >= 0xFFFFFF00LL))
+                   a->N % 256 != 0 || a->ldc % 8 != 0 || (long long)a->M * a->ldc * 4 >= 0xFFFFFF00LL))
     return DP_ERR_ARG;
   if (lnc && (!(a->ln_part_in || a->ln_rs_in) || (a->ln_part_in && a->ln_rs_in) || !a->ln_colsum || a->K != 1024 ||
               a->accumulate || a->c_dtype == DP_F32 || a->gamma || (a->act != DP_ACT_NONE && a->act != DP_ACT_GELU) ||
@@ -145,6 +145,9 @@ int gemm_plan(const dp_gemm_args* a, GemmP& p, int& tile) {
   const bool ws_ok = a->workspace && a->workspace_bytes >= dp_gemm_workspace_size();
   const int dbg = g_dbg_flags.load(std::memory_order_relaxed);
   tile = a->tile;
+  // ln_rs_in exists on the persistent 8-phase engine only: DP_TILE_AUTO means that engine at every
+  // size (not just where the cost model below would pick it), so AUTO serves what the hint serves
+  if (a->ln_rs_in) tile = DP_TILE_P8PH_256x256;
   if (a->store_mode == DP_STORE_HEAD_PS) {
     // 32-column parity groups must not straddle a wave's columns (TN = 32 or 64); the patch-conv
     // engine (one parity per wave) only when asked for: at 768^2 it runs 347 - 355 us in-frame vs

@@ -913,7 +913,8 @@ int dp_cluster_shapes(const double* points, const int32_t* n_dev, int32_t n_max,
  * 2 * voxel_size, max_nn = 30)) and orient_normals_towards_camera_location([0, 0, 0]).  (Its first
  * estimate_normals, on the full cloud, is overwritten by the one after down-sampling and is skipped
  * here.)  Their product, an oriented point set, is what a surface reconstructor takes as input; Poisson
- * and ball-pivoting reconstruction and the mesh clean-up are out of scope.  The ground, clean and
+ * and ball-pivoting reconstruction and the non-manifold clean-up are out of scope (the reference's third
+ * method is the "Triangle mesh" section below).  The ground, clean and
  * cluster sections' conventions hold: fp64 points [n_max][3], n_dev a device int32 (NULL: n_max;
  * clamped to [0, n_max]), n_max = 0 and *n_dev = 0 valid, everything on the caller's stream with no
  * synchronisation and no host read-back, each fp64 product, sum and difference rounded on its own (no
@@ -1272,6 +1273,113 @@ int dp_boundary_counts(const float* pred, int64_t ld_pred, const void* target, i
 int dp_boundary_edges(const float* depth, int64_t ld, int32_t H, int32_t W, double t, int32_t thinned,
                       uint8_t* maps /* device, 4 planes of H*W bytes, 0 outside each map's extent */, void* ws,
                       int64_t ws_bytes, dp_stream_t stream);
+
+/*
+ * ---- Triangle mesh (additive to ABI 20, csrc/dp_mesh.hip) -------------------------------------------
+ * The reference's third meshing method, `--mesh_method simple` (create_simple_triangulated_mesh,
+ * pointcloud_to_mesh.py:423-465), and the search under it: for every point of the down-sampled cloud the 6
+ * nearest other points, the 5 triangles (i, n_j, n_j+1) over them, then remove_degenerate_triangles and
+ * remove_duplicated_triangles.  The same search with k = 20 is get_average_point_distance (:397-421), from
+ * which ball pivoting takes its radii.  The block is additive: no existing entry point or layout changes,
+ * and DP_ABI_VERSION stays 20.  The point-cloud sections' conventions hold: fp64 points [n_max][3], n_dev a
+ * device int32 (NULL: n_max; clamped to [0, n_max]), n_max = 0 and *n_dev = 0 valid, everything on the
+ * caller's stream with no synchronisation and no host read-back, each fp64 product, sum and difference
+ * rounded on its own (no FMA), argument errors returned as DP_ERR_* before any launch.  Rows at or beyond the
+ * live count are neither read nor written.
+ *   workspace  >= dp_mesh_workspace_size(n_max, t_max) bytes of device memory, 8-byte aligned, owned by the
+ *              call until the stream has passed it (content need not be initialised).  A call on points
+ *              needs (its n_max, 0), dp_mesh_clean_triangles (0, its t_max); a buffer sized for both serves
+ *              every call.  About 85 bytes per point or 61 per triangle, whichever is more (the sort's
+ *              workspace included).
+ *   stats_out  fp64 [8], per call as listed below.
+ * Open3D was not available to check against, so, as for dp_clean_stray and the oriented mesh points, the
+ * numbered rules below are the specification (restated in tests/mesh_numpy.py, which is pinned to scipy's
+ * cKDTree).
+ * Not built: Poisson and ball-pivoting reconstruction (Open3D internals: their results depend on its octree
+ * and on the order of its front), remove_duplicated_vertices (a no-op on a voxel grid's output) and
+ * remove_non_manifold_edges (it removes triangles in the iteration order of an Open3D hash map, which cannot
+ * be specified).
+ *
+ * Exact k nearest (dp_knn_exact).
+ *   1. Participants are the finite live rows.  For row i the list holds the k participants j != i that are
+ *      smallest by (d2, j), d2 = (dx*dx + dy*dy) + dz*dz -- the expression of dp_clean_stray and
+ *      dp_knn_search.  k in [1, 64] (else DP_ERR_SHAPE).
+ *   2. nbr_out        int32 [n_max][k]: row i's neighbours in ascending (d2, row) order, then -1
+ *      nbr_count_out  int32 [n_max]: their number, min(k, participants - 1); 0 for a non-finite row
+ *      d2_out         fp64 [n_max][k], may be NULL: the listed d2; entries past the count are not written
+ *   3. cell_edge (finite and > 0, else DP_ERR_SHAPE) is the search grid's cell size: a speed parameter that
+ *      never changes a list or a count.  The grid: per axis origin = the minimum over the participants, cell =
+ *      floor((v - origin) / g) with g = cell_edge * (1 + 2^-20), clamped to [0, 2^21 - 2].
+ *   4. The ring of row i is the smallest r >= 0 such that its list is full (k entries) and its largest d2 is
+ *      strictly below (r * cell_edge) * (r * cell_edge) (fp64, r exact), or such that the cube of cells within
+ *      Chebyshev distance r of row i's cell covers every participant's cell, whichever r is smaller.  It is
+ *      the number of cell rings a walk outward from the row's cell has to take: with g above cell_edge, a
+ *      cell further than r cells away holds no point that near.
+ *   5. stats_out: finite rows, non-finite rows, finite rows with fewer than k neighbours, the largest ring
+ *      of any finite row, error flag, 0, 0, 0.
+ *   6. Error flag (device side): an axis would need more than 2^21 - 2 cells ((max - origin) / g).  Then every
+ *      count is 0, every list -1, the third entry of stats_out the number of finite rows and the ring 0.
+ *   7. Stated difference: Open3D's search_knn_vector_3d(p, k + 1) lists the query itself at position 0, which
+ *      the reference drops; here the query is excluded by identity.  The two differ only for exact duplicate
+ *      points, which a voxel grid never produces.  Open3D's order among equal distances is unspecified; here
+ *      it is by row.
+ * Method: dp_knn_search's grid (dp_sort_pairs on (cell, row), coordinates gathered into cell order, a run of
+ * z-adjacent cells of one (x, y) cell row is one key range found by binary search).  One wave per query.
+ * Ring r is the shell of cells at Chebyshev distance exactly r: the 8 r cell rows on the square's rim with
+ * 2 r + 1 cells each, and two single cells for each of the (2 r - 1)^2 rows inside; the lanes take one range's
+ * pair of binary searches each, the ranges' candidates are numbered by a prefix sum over the lanes and go 64
+ * at a time through dp_knn_search's bitonic merge into a running best of one entry per lane.  The loop is
+ * wave-uniform and ends after ring r by rule 4.  No scratch, no per-thread arrays, no LDS.
+ * Bound: a query whose k-th neighbour lies R cells away visits O(R^2) cell rows (O(R^3) ranges) up to
+ * R = 8; a query still open after ring 8 starts again over every participant in sorted order (n / 64 batches,
+ * nearly all rejected by one comparison), so the work is bounded whatever the cloud and cell_edge are, and a
+ * cell_edge far below the point spacing costs O(n^2 / 64).
+ *
+ * Mean neighbour distance (dp_mesh_mean_distance), from d2_out and nbr_count_out of a dp_knn_exact call.
+ *   1. Per row with m > 0 listed neighbours: (sqrt(d2[0]) + sqrt(d2[1]) + ... + sqrt(d2[m-1])) / m, summed in
+ *      list order.
+ *   2. mean_out[0] = the sum of those over the rows with m > 0, divided by their number (0 without any);
+ *      mean_out[1] = their number.  Order of the sum: 256 partial sums, partial t taking rows t, t + 256, ...
+ *      in turn; within each group of 64 partials the butterfly v[l] += v[l ^ o] for o = 32, 16, ..., 1; the
+ *      four groups' sums added in group order.
+ *   3. Stated difference: get_average_point_distance averages over 1000 randomly sampled rows; this is its
+ *      deterministic form over all of them.
+ *
+ * Fan (dp_mesh_fan), the reference's loop at :448-457, from the lists of a dp_knn_exact call.
+ *   1. Row i with m = min(nbr_count[i], k) listed neighbours gives the triangles (i, nbr[i][j], nbr[i][j+1])
+ *      for j = 0 .. m - 2, at slot i * (k - 1) + j of tri_out, int32 [n_max * (k - 1)][3]; the other slots
+ *      of a live row are (-1, -1, -1).
+ *   2. n_max * (k - 1) must be below 2^31 / 3 (else DP_ERR_SHAPE); k = 1 has no slots.
+ *
+ * Triangle clean-up (dp_mesh_clean_triangles): remove_degenerate_triangles, then remove_duplicated_triangles,
+ * on a plain list tri_in int32 [t_max][3] with live count t_dev over n_vertices vertices.
+ *   1. A triangle with an index outside [0, n_vertices) is dropped (`invalid`: how the fan's empty slots
+ *      leave); of the others, one with two equal indices is dropped (`degenerate`).
+ *   2. The canonical form of a triangle is its cyclic rotation with the smallest index first: (a, b, c),
+ *      (b, c, a) and (c, a, b) are one triangle, (a, c, b) is another (the orientation is kept).
+ *   3. Of the triangles sharing a canonical form the one at the smallest input position is kept, as it came
+ *      (not rotated); the others count as `duplicated`.
+ *   4. tri_out int32 [t_max][3] (not tri_in): the kept triangles in ascending input position; *t_out_dev their
+ *      number; rows at or beyond it are not written.
+ *   5. stats_out: input, invalid, degenerate, duplicated, kept, error flag (always 0: nothing can go wrong
+ *      on the device), 0, 0.  Any n_vertices in [0, 2^31) works.
+ * Method: three indices do not fit one 64-bit key above 2^21 vertices, so two stable passes of dp_sort_pairs
+ * with the input position as payload: by the canonical third index, then by (first << 32) | second; dropped
+ * triangles sort last.  A run's head is then its smallest position; the heads are flagged by position,
+ * scanned (dp_points.h) and compacted.
+ */
+int64_t dp_mesh_workspace_size(int64_t n_max, int64_t t_max);
+int dp_knn_exact(const double* points, const int32_t* n_dev, int32_t n_max, int32_t k, double cell_edge,
+                 int32_t* nbr_out, int32_t* nbr_count_out, double* d2_out, double* stats_out, void* workspace,
+                 int64_t workspace_bytes, dp_stream_t stream);
+int dp_mesh_mean_distance(const double* d2, const int32_t* nbr_count, const int32_t* n_dev, int32_t n_max, int32_t k,
+                          double* mean_out /* device, fp64 [2] */, void* workspace, int64_t workspace_bytes,
+                          dp_stream_t stream);
+int dp_mesh_fan(const int32_t* nbr, const int32_t* nbr_count, const int32_t* n_dev, int32_t n_max, int32_t k,
+                int32_t* tri_out, dp_stream_t stream);
+int dp_mesh_clean_triangles(const int32_t* tri_in, const int32_t* t_dev, int32_t t_max, int32_t n_vertices,
+                            int32_t* tri_out, int32_t* t_out_dev, double* stats_out, void* workspace,
+                            int64_t workspace_bytes, dp_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -57,6 +57,7 @@ EXPORTS = (
     "dp_floorplan_workspace_size", "dp_occupancy_grid", "dp_grid_morphology", "dp_grid_regions", "dp_floorplan_image",
     "dp_shape_rectangles", "dp_lshape_workspace_size", "dp_lshape_split",
     "dp_boundary_workspace_size", "dp_boundary_counts", "dp_boundary_edges",
+    "dp_mesh_workspace_size", "dp_knn_exact", "dp_mesh_mean_distance", "dp_mesh_fan", "dp_mesh_clean_triangles",
 )
 
 
@@ -172,6 +173,11 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "dp_boundary_workspace_size": [i32, i32, i32],
         "dp_boundary_counts": [vp, i64, vp, i64, i32, i32, i32, ctypes.POINTER(f64), i32, vp, vp, i64, vp],
         "dp_boundary_edges": [vp, i64, i32, i32, f64, i32, vp, vp, i64, vp],
+        "dp_mesh_workspace_size": [i64, i64],
+        "dp_knn_exact": [vp, vp, i32, i32, f64, vp, vp, vp, vp, vp, i64, vp],
+        "dp_mesh_mean_distance": [vp, vp, vp, i32, i32, vp, vp, i64, vp],
+        "dp_mesh_fan": [vp, vp, vp, i32, i32, vp, vp],
+        "dp_mesh_clean_triangles": [vp, vp, i32, i32, vp, vp, vp, vp, i64, vp],
     }
     for name, argtypes in sig.items():
         fn = getattr(lib, name)
@@ -186,6 +192,7 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.dp_floorplan_workspace_size.restype = ctypes.c_int64
     lib.dp_lshape_workspace_size.restype = ctypes.c_int64
     lib.dp_boundary_workspace_size.restype = ctypes.c_int64
+    lib.dp_mesh_workspace_size.restype = ctypes.c_int64
     lib.dp_gemm_debug_flags.argtypes = [ctypes.c_int]
     lib.dp_gemm_debug_flags.restype = ctypes.c_int
     ver = lib.dp_abi_version()

@@ -29,6 +29,12 @@ Oriented mesh points (the start of the reference's meshing step, `pointcloud_to_
 values) -- csrc/dp_normals.hip, no Open3D, no host read-back; `write_ply_normals` / `read_ply_normals` are the
 PLY writer and reader for a cloud with normals.
 
+Triangle mesh (the reference's `--mesh_method simple`, `pointcloud_to_mesh.py:397-465`): `knn_exact` (the k nearest
+other rows, exactly), `fan_triangles`, `clean_triangles`, `triangulate`, `simple_mesh` and `mean_neighbor_distance`
+(the deterministic `get_average_point_distance`) -- csrc/dp_mesh.hip, no Open3D, no host read-back;
+`mesh_ply_records_async`, `write_mesh_ply` and `read_mesh_ply` are the PLY writer and reader for a mesh.
+Not built: Poisson and ball-pivoting reconstruction, `remove_duplicated_vertices`, `remove_non_manifold_edges`.
+
 Occupancy floor plan (the reference's `cleaned_pointcloud_to_floorplan.py` up to its contour tracing):
 `occupancy_grid`, `grid_morphology`, `grid_regions`, `floorplan_image` and `floor_plan` (all four with the
 reference's height-threshold values) -- csrc/dp_floorplan.hip, no OpenCV, no host read-back;
@@ -1040,6 +1046,212 @@ def read_ply_normals(path: str) -> Tuple[np.ndarray, np.ndarray, Optional[np.nda
     dt = [("p", "<f8", 3), ("n", "<f8", 3)] + ([("c", "u1", 3)] if any("red" in l for l in lines) else [])
     rec = np.frombuffer(data[end:], dtype=dt, count=n)
     return rec["p"].copy(), rec["n"].copy(), (rec["c"].copy() if len(dt) == 3 else None)
+
+
+# ---- triangle mesh: exact k nearest, fan, triangle clean-up (csrc/dp_mesh.hip) -----------------------
+
+KNN_EXACT_STATS = ("finite", "non_finite", "few_neighbors", "max_ring", "error", "reserved0", "reserved1", "reserved2")
+TRIANGLE_STATS = ("input", "invalid", "degenerate", "duplicated", "kept", "error", "reserved0", "reserved1")
+MAX_K = 64
+
+_MESH = "the triangle mesh runs on the ROCm device (csrc/dp_mesh.hip)"
+
+
+def _check_knn(k, cell_edge) -> None:
+    if not 1 <= int(k) <= MAX_K:
+        raise ValueError(f"k must be in [1, {MAX_K}] (got {k})")
+    if not (np.isfinite(float(cell_edge)) and float(cell_edge) > 0):
+        raise ValueError(f"cell_edge must be finite and > 0 (got {cell_edge})")
+
+
+def knn_exact(points: torch.Tensor, count=None, k: int = 6, cell_edge: float = 0.1):
+    """The k nearest other rows of every row (`dp_knn_exact`), what Open3D's `search_knn_vector_3d(p, k + 1)[1:]` lists:
+    (neighbours (N, k) int32 in ascending (squared distance, row) order, padded with -1; their number (N,) int32 --
+    min(k, finite rows - 1), 0 for a non-finite row; their squared distances (N, k) float64, (dx*dx + dy*dy) + dz*dz;
+    stats (8,) float64 in `KNN_EXACT_STATS` order).  `cell_edge` is the search grid's cell size, a speed parameter that
+    never changes the result.  Asynchronous, no read-back; rows past `count` are not written.  A cloud spanning more
+    than 2^21 - 2 cells on an axis raises stats["error"] and every count is 0.  Stated difference: the query is
+    excluded by identity, not as the list's first entry, so an exact duplicate of it is listed."""
+    _check_knn(k, cell_edge)
+    lib, pts, n, count, cptr, stream = _points_args(points, count, _MESH)
+    dev = pts.device
+    ws = torch.empty(int(lib.dp_mesh_workspace_size(n, 0)), dtype=torch.uint8, device=dev)
+    nbr = torch.empty(n, int(k), dtype=torch.int32, device=dev)
+    cnt = torch.empty(n, dtype=torch.int32, device=dev)
+    d2 = torch.empty(n, int(k), dtype=torch.float64, device=dev)
+    stats = torch.empty(8, dtype=torch.float64, device=dev)
+    check(lib.dp_knn_exact(pts.data_ptr(), cptr, n, int(k), float(cell_edge), nbr.data_ptr(), cnt.data_ptr(), d2.data_ptr(),
+                           stats.data_ptr(), ws.data_ptr(), ws.numel(), stream), "dp_knn_exact")
+    return nbr, cnt, d2, stats
+
+
+def _lists_args(nbr: torch.Tensor, nbr_count: torch.Tensor, count):
+    """(lib, N, k, device count pointer or None, stream, the count tensor) of a call on the lists of `knn_exact`."""
+    if nbr.device.type != "cuda":
+        raise _lib.DPError(_MESH)
+    if nbr_count.device != nbr.device:
+        raise _lib.DPError("nbr and nbr_count must be on one device")
+    if nbr.dim() != 2 or not nbr.is_contiguous() or not 1 <= nbr.shape[1] <= MAX_K:
+        raise ValueError(f"the lists must be a contiguous (N, k <= {MAX_K}) tensor")
+    if nbr_count.dtype != torch.int32 or tuple(nbr_count.shape) != (nbr.shape[0],) or not nbr_count.is_contiguous():
+        raise ValueError("nbr_count must be a contiguous (N,) int32 tensor")
+    count = _count_tensor(count, nbr.device)
+    return (_lib.load(), nbr.shape[0], nbr.shape[1], None if count is None else count.data_ptr(),
+            torch.cuda.current_stream(nbr.device).cuda_stream, count)
+
+
+def fan_triangles(nbr: torch.Tensor, nbr_count: torch.Tensor, count=None) -> torch.Tensor:
+    """The reference's triangle loop (pointcloud_to_mesh.py:448-457) over the lists of `knn_exact` (`dp_mesh_fan`):
+    row i with m listed neighbours gives (i, nbr[i, j], nbr[i, j + 1]) for j < m - 1 at slot i * (k - 1) + j of the
+    (N * (k - 1), 3) int32 result; a live row's other slots are (-1, -1, -1), which `clean_triangles` drops.
+    Asynchronous; the slots of rows past `count` are not written."""
+    if nbr.dtype != torch.int32:
+        raise ValueError("nbr must be int32")
+    lib, n, k, cptr, stream, _ = _lists_args(nbr, nbr_count, count)
+    if n * (k - 1) >= 2 ** 31 // 3:
+        raise ValueError("at most 2^31 / 3 - 1 triangle slots")
+    tri = torch.empty(n * (k - 1), 3, dtype=torch.int32, device=nbr.device)
+    check(lib.dp_mesh_fan(nbr.data_ptr(), nbr_count.data_ptr(), cptr, n, k, tri.data_ptr(), stream), "dp_mesh_fan")
+    return tri
+
+
+def clean_triangles(tri: torch.Tensor, n_vertices: int, count=None):
+    """Open3D's `remove_degenerate_triangles` then `remove_duplicated_triangles` on a plain (T, 3) int32 list
+    (`dp_mesh_clean_triangles`): (triangle buffer (T, 3), device int32 count, stats (8,) float64 in `TRIANGLE_STATS`
+    order).  Dropped: a triangle with an index outside [0, n_vertices), one with two equal indices, and every later
+    copy of a triangle -- two are copies when they are cyclic rotations of each other; the mirror image is another
+    triangle.  The kept ones come in their input order and as they were.  Asynchronous, no read-back; `count`: the
+    live triangles (int or device int32)."""
+    if tri.dtype != torch.int32 or tri.dim() != 2 or tri.shape[1] != 3:
+        raise ValueError("tri must be a (T, 3) int32 tensor")
+    if not 0 <= int(n_vertices) < 2 ** 31:
+        raise ValueError(f"n_vertices must be in [0, 2^31) (got {n_vertices})")
+    if tri.device.type != "cuda":
+        raise _lib.DPError(_MESH)
+    src = tri.contiguous()
+    t, dev = src.shape[0], src.device
+    if t >= 2 ** 31:
+        raise ValueError("at most 2^31 - 1 triangles")
+    count = _count_tensor(count, dev)
+    lib = _lib.load()
+    ws = torch.empty(int(lib.dp_mesh_workspace_size(0, t)), dtype=torch.uint8, device=dev)
+    out = torch.empty_like(src)
+    n_out = torch.empty(1, dtype=torch.int32, device=dev)
+    stats = torch.empty(8, dtype=torch.float64, device=dev)
+    check(lib.dp_mesh_clean_triangles(src.data_ptr(), None if count is None else count.data_ptr(), t, int(n_vertices),
+                                      out.data_ptr(), n_out.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(),
+                                      torch.cuda.current_stream(dev).cuda_stream), "dp_mesh_clean_triangles")
+    return out, n_out, stats
+
+
+def triangulate(points: torch.Tensor, count=None, neighbors: int = 6, cell_edge: float = 0.1):
+    """`knn_exact(k = neighbors)`, `fan_triangles`, `clean_triangles` over one point set: (triangle buffer, device int32
+    triangle count, knn stats, triangle stats).  The reference's create_simple_triangulated_mesh on points that are
+    already down-sampled.  Nothing synchronised."""
+    if not 2 <= int(neighbors) <= MAX_K:
+        raise ValueError(f"neighbors must be in [2, {MAX_K}] (got {neighbors})")
+    nbr, cnt, _, kst = knn_exact(points, count, neighbors, cell_edge)
+    n, slots = nbr.shape[0], int(neighbors) - 1
+    tri = fan_triangles(nbr, cnt, count)
+    live = None
+    if count is not None:                   # the fan's live slots, still on the device
+        live = (_count_tensor(count, nbr.device).clamp(0, n) * slots).to(torch.int32)
+    out, n_tri, tst = clean_triangles(tri, n, live)
+    return out, n_tri, kst, tst
+
+
+def simple_mesh(points: torch.Tensor, colors: Optional[torch.Tensor] = None, count=None, voxel_size: float = 0.05,
+                neighbors: int = 6):
+    """The reference's `--mesh_method simple` (pointcloud_to_mesh.py:313-395 with create_simple_triangulated_mesh,
+    :423-465): `voxel_downsample(voxel_size)`, then for every voxel its `neighbors` nearest others (`knn_exact` on a
+    grid of 2 * voxel_size), the fan of triangles over them, and the removal of degenerate and duplicated triangles.
+    Returns (vertex buffer, colour buffer or None, device int32 vertex count, triangle buffer, device int32 triangle
+    count, {"voxel": ..., "knn": ..., "triangles": ...} stats); the first `count` rows of each are the mesh.  On the
+    device, nothing synchronised.  Not built: remove_duplicated_vertices (nothing to do after a voxel grid) and
+    remove_non_manifold_edges (Open3D's result depends on a hash map's order)."""
+    out, cout, _, _, n_out, vst = voxel_downsample(points, colors, count, voxel_size)
+    tri, n_tri, kst, tst = triangulate(out, n_out, neighbors, 2.0 * float(voxel_size))
+    return out, cout, n_out, tri, n_tri, {"voxel": vst, "knn": kst, "triangles": tst}
+
+
+def mean_neighbor_distance(points: torch.Tensor, count=None, k: int = 20, cell_edge: float = 0.1) -> torch.Tensor:
+    """The reference's `get_average_point_distance(pcd, k)` without its random sample (`dp_mesh_mean_distance` on the
+    lists of `knn_exact`): per row the mean of sqrt(d2) over its listed neighbours in list order, then the mean over
+    the rows that have any -- a device float64 scalar, 0 without such a row.  The reference's ball-pivoting radii are
+    [2, 4, 8, 16] times it.  Stated difference: the reference averages over 1000 randomly sampled rows."""
+    _, cnt, d2, _ = knn_exact(points, count, k, cell_edge)
+    lib, n, k, cptr, stream, _ = _lists_args(d2, cnt, count)
+    ws = torch.empty(int(lib.dp_mesh_workspace_size(n, 0)), dtype=torch.uint8, device=d2.device)
+    out = torch.empty(2, dtype=torch.float64, device=d2.device)
+    check(lib.dp_mesh_mean_distance(d2.data_ptr(), cnt.data_ptr(), cptr, n, k, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                    stream), "dp_mesh_mean_distance")
+    return out[0]
+
+
+BALL_PIVOT_FACTORS = (2, 4, 8, 16)      # the reference's radii, as multiples of the mean neighbour distance
+PLY_FACE_RECORD = 13                    # bytes per face: uchar 3, then three uint32 vertex indices
+
+
+def _mesh_ply_header(n: int, t: int, colored: bool) -> bytes:
+    props = ["property double x", "property double y", "property double z"]
+    if colored:
+        props += ["property uchar red", "property uchar green", "property uchar blue"]
+    return ("\n".join(["ply", "format binary_little_endian 1.0", f"element vertex {n}", *props, f"element face {t}",
+                       "property list uchar uint vertex_indices", "end_header"]) + "\n").encode("ascii")
+
+
+def mesh_ply_records_async(xyz: torch.Tensor, cols: Optional[torch.Tensor], tri: torch.Tensor):
+    """The records `write_mesh_ply` writes, interleaved on the device: vertex records ((N, 27) uint8 as
+    `ply_records_async` makes them, (N, 24) without colours) and face records ((T, 13) uint8: the byte 3, then the
+    three indices as little-endian uint32).  Queued on the current stream, no sync."""
+    n, t = xyz.shape[0], tri.shape[0]
+    if cols is not None:
+        vrec = ply_records_async(xyz.contiguous(), cols)
+    else:
+        vrec = xyz.contiguous().view(torch.uint8).view(n, 24).clone()
+    frec = torch.empty(t, PLY_FACE_RECORD, dtype=torch.uint8, device=tri.device)
+    frec[:, 0] = 3
+    frec[:, 1:].copy_(tri.contiguous().view(torch.uint8).view(t, 12))
+    return vrec, frec
+
+
+def write_mesh_ply(path: str, vertex_records: np.ndarray, face_records: np.ndarray) -> str:
+    """Binary little-endian PLY of a triangle mesh from records already in file layout (`mesh_ply_records_async`):
+    `element vertex` with double x, y, z (+ uchar red, green, blue), then `element face` with `property list uchar
+    uint vertex_indices`.  Stated difference: the reference's default file is an OBJ written by Open3D."""
+    vrec = np.ascontiguousarray(vertex_records, dtype=np.uint8)
+    frec = np.ascontiguousarray(face_records, dtype=np.uint8)
+    if vrec.ndim != 2 or vrec.shape[1] not in (PLY_RECORD, PLY_RECORD - 3):
+        raise ValueError(f"vertex records must be (n, {PLY_RECORD}) or (n, {PLY_RECORD - 3}) uint8")
+    if frec.ndim != 2 or frec.shape[1] != PLY_FACE_RECORD:
+        raise ValueError(f"face records must be (t, {PLY_FACE_RECORD}) uint8")
+    if not path.endswith(".ply"):
+        path = path + ".ply"
+    with open(path, "wb") as f:
+        f.write(_mesh_ply_header(vrec.shape[0], frec.shape[0], vrec.shape[1] == PLY_RECORD))
+        f.write(memoryview(vrec.reshape(-1)))            # flat first: a frame may leave no points
+        f.write(memoryview(frec.reshape(-1)))
+    return path
+
+
+def read_mesh_ply(path: str) -> Tuple[np.ndarray, Optional[np.ndarray], np.ndarray]:
+    """Reader for the files `write_mesh_ply` produces: (points (n, 3) float64, colours (n, 3) uint8 or None, triangles
+    (t, 3) uint32)."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    lines = data[:end].decode("ascii").splitlines()
+    n = int(next(l for l in lines if l.startswith("element vertex")).split()[-1])
+    face = [l for l in lines if l.startswith("element face")]
+    if not face or "property list uchar uint vertex_indices" not in lines:
+        raise ValueError(f"{path} has no faces")
+    t = int(face[0].split()[-1])
+    dt = [("p", "<f8", 3)] + ([("c", "u1", 3)] if any("red" in l for l in lines) else [])
+    vert = np.frombuffer(data[end:], dtype=dt, count=n)
+    faces = np.frombuffer(data[end + vert.nbytes:], dtype=[("k", "u1"), ("v", "<u4", 3)], count=t)
+    if t and not (faces["k"] == 3).all():
+        raise ValueError(f"{path} has faces that are not triangles")
+    return vert["p"].copy(), (vert["c"].copy() if len(dt) == 2 else None), faces["v"].copy()
 
 
 # ---- occupancy floor plan: raster, morphology, regions, picture (csrc/dp_floorplan.hip) -------------

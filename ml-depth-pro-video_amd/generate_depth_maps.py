@@ -258,19 +258,20 @@ def boundary_target_path(image_path: str, boundary_dir: str) -> str:
 
 def plan_frames(image_paths, output_dir: str, world: int, rank: int, resume: bool, cleaned: bool = False,
                 clustered: bool = False, shaped: bool = False, oriented: bool = False, floor: bool = False,
-                boundary: Optional[str] = None, stages=()) -> List[int]:
+                boundary: Optional[str] = None, stages=(), meshed: bool = False) -> List[int]:
     """Indices of the frames this rank processes: the frames still to do (all of them, or with
     `resume` those with an output file missing -- decided by rank 0 alone and broadcast before
     any rank writes, so every rank shards the same list), dealt round-robin over the ranks.
     Missing: a frame without its `{base}_depth.png`, or without a file that a stage which is on requires
     (`Stage.suffixes`).  On are the stages named in `stages`, and `cleaned` (--clean_pointcloud), `clustered`
-    (--cluster_pointcloud), `shaped` (--fit_shapes), `oriented` (--mesh_points), `floor` (--floor_plan), `boundary`
-    (--boundary_dir: only a frame with a target `{base}.npy` in that directory needs its `{base}_boundary.json`)."""
+    (--cluster_pointcloud), `shaped` (--fit_shapes), `oriented` (--mesh_points), `meshed` (--simple_mesh), `floor`
+    (--floor_plan), `boundary` (--boundary_dir: only a frame with a target `{base}.npy` in that directory needs its `{base}_boundary.json`)."""
     todo = list(range(len(image_paths)))
     if resume:
         if rank == 0:
             on = set(stages) | {name for name, flag in (("clean", cleaned), ("cluster", clustered), ("shapes", shaped),
-                                                        ("mesh", oriented), ("floor", floor), ("boundary", boundary)) if flag}
+                                                        ("mesh", oriented), ("trimesh", meshed), ("floor", floor),
+                                                        ("boundary", boundary)) if flag}
             need = ["_depth.png"] + [s for st in STAGES if st.name in on and st.name != "boundary" for s in st.suffixes]
 
             def done(k):
@@ -307,7 +308,7 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                               cluster_height=1.3, cluster_max_points=100000, fit_shapes=False,
                               circularity_threshold=0.85, mesh_points=False, voxel_size=0.05, normals_max_nn=30,
                               floor_plan=False, floor_resolution=0.1, floor_height=1.3, floor_min_area=0.025,
-                              boundary_dir=None, split_l_shapes=False):
+                              boundary_dir=None, split_l_shapes=False, simple_mesh=False, mesh_neighbors=6):
     """Directory loop (reference :153-206), pipelined decode -> GPU -> encode, frame-sharded across ranks.
 
     Every rank writes its own frames' files; each frame has exactly one owner.  resume=True skips
@@ -352,6 +353,11 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
     normals over radius 2 * voxel_size and at most normals_max_nn neighbours, oriented towards the origin)
     and writes `{base}_oriented.ply` (double x y z nx ny nz + uchar rgb) and `{base}_oriented.json`
     (parameters, point count, both statistics).
+    simple_mesh=True (implies mesh_points) meshes those voxels as the reference's `--mesh_method simple` does
+    (`PC.triangulate`: every voxel's mesh_neighbors nearest others, the fan of triangles over them, degenerate and
+    duplicated triangles removed) and writes `{base}_mesh.ply` (the vertices of `{base}_oriented.ply` without normals,
+    then `element face`) and `{base}_mesh.json` (parameters, counts, both statistics, the mean distance to the 20
+    nearest voxels and the reference's four ball-pivoting radii).
     boundary_dir=DIR scores each frame whose target `DIR/{base}.npy` exists and has the depth's shape with the Depth Pro
     boundary metric (`depth_pro.eval.boundary_metrics`), from the device depth before its read-back:
     a float32 target is a depth (SI_boundary_F1), a bool or uint8 one a mask (SI_boundary_Recall, the raw values
@@ -496,6 +502,11 @@ def check_mesh(voxel_size, max_nn) -> None:
         raise ValueError(f"--voxel_size must be finite and > 0 (got {voxel_size})")
     if not 1 <= int(max_nn) <= PC.MAX_NN:
         raise ValueError(f"--normals_max_nn must be in [1, {PC.MAX_NN}] (got {max_nn})")
+
+
+def check_mesh_neighbors(neighbors) -> None:
+    if not 2 <= int(neighbors) <= PC.MAX_K:
+        raise ValueError(f"--mesh_neighbors must be in [2, {PC.MAX_K}] (got {neighbors})")
 
 
 def check_floor(resolution, height, min_area) -> None:
@@ -682,6 +693,7 @@ def _queue_mesh(frame: dict, p: dict) -> dict:
     """The oriented point set of the cleaned cloud (--mesh_points): voxel grid, normals, orientation, PLY records.  Only
     the voxel count and the statistics are copied here; the records stay on the device and the writer fetches `count`."""
     op, oc, on, onrm, vst, nst = PC.oriented_points(frame["xyz"], frame["cols"], frame["count"], p["voxel_size"], p["max_nn"])
+    frame.update(voxels=op, voxel_cols=oc, n_voxels=on, voxel_size=p["voxel_size"])      # what --simple_mesh meshes
     return {"count": _pinned(on.reshape(())), "voxel_stats": _pinned(vst), "normal_stats": _pinned(nst),
             "records": PC.ply_normals_records_async(op, onrm, oc)}
 
@@ -704,6 +716,44 @@ def _write_oriented(base: str, params: dict, out: dict) -> None:
                "voxel_stats": {k: float(v) for k, v in zip(PC.VOXEL_STATS, m["voxel_stats"].numpy())},
                "normal_stats": {k: float(v) for k, v in zip(PC.NORMAL_STATS, m["normal_stats"].numpy())}}
     with open(base + "_oriented.json", "w") as f:
+        json.dump(summary, f, indent=1)
+
+
+def _queue_trimesh(frame: dict, p: dict) -> dict:
+    """The reference's simple mesh over the voxels the mesh stage has left on the device (--simple_mesh): the nearest
+    neighbours of every voxel, the fan of triangles, the clean-up, the PLY records, and the mean distance to the 20 nearest
+    from which the reference takes its ball-pivoting radii.  Counts and statistics are copied here; the writer fetches
+    the records."""
+    vox, n_vox, edge = frame["voxels"], frame["n_voxels"], 2.0 * frame["voxel_size"]
+    tri, n_tri, kst, tst = PC.triangulate(vox, n_vox, p["neighbors"], edge)
+    vrec, frec = PC.mesh_ply_records_async(vox, frame["voxel_cols"], tri)
+    return {"vertices": _pinned(n_vox.reshape(())), "triangles": _pinned(n_tri.reshape(())), "knn_stats": _pinned(kst),
+            "triangle_stats": _pinned(tst), "mean_distance": _pinned(PC.mean_neighbor_distance(vox, n_vox, 20, edge)),
+            "vertex_records": vrec, "face_records": frec}
+
+
+def _write_trimesh(base: str, params: dict, out: dict) -> None:
+    """Writer-thread side (after the frame's event): fetch the live records on a stream of this thread's own, then
+    `{base}_mesh.ply` and `{base}_mesh.json`."""
+    m, p = out["trimesh"], params["trimesh"]
+    side = torch.cuda.Stream(m["vertex_records"].device)
+    host = []
+    with torch.cuda.stream(side):
+        for rec, count in ((m["vertex_records"], m["vertices"]), (m["face_records"], m["triangles"])):
+            n = max(0, min(int(count), rec.shape[0]))
+            host.append(torch.empty((n, rec.shape[1]), dtype=rec.dtype, pin_memory=True))
+            host[-1].copy_(rec[:n], non_blocking=True)
+    side.synchronize()
+    PC.write_mesh_ply(base + "_mesh.ply", host[0].numpy(), host[1].numpy())
+    mean = float(m["mean_distance"])
+    summary = {"parameters": {"voxel_size": params["mesh"]["voxel_size"], "neighbors": p["neighbors"],
+                              "cell_edge": 2.0 * params["mesh"]["voxel_size"], "method": "simple"},
+               "vertices": host[0].shape[0], "triangles": host[1].shape[0],
+               "knn_stats": {k: float(v) for k, v in zip(PC.KNN_EXACT_STATS, m["knn_stats"].numpy())},
+               "triangle_stats": {k: float(v) for k, v in zip(PC.TRIANGLE_STATS, m["triangle_stats"].numpy())},
+               "mean_neighbor_distance": mean, "mean_neighbor_distance_k": 20,
+               "ball_pivoting_radii": [f * mean for f in PC.BALL_PIVOT_FACTORS]}
+    with open(base + "_mesh.json", "w") as f:
         json.dump(summary, f, indent=1)
 
 
@@ -796,6 +846,11 @@ def _mesh_params(o: dict) -> dict:
     return {"voxel_size": float(o["voxel_size"]), "max_nn": int(o["normals_max_nn"])}
 
 
+def _trimesh_params(o: dict) -> dict:
+    check_mesh_neighbors(o["mesh_neighbors"])
+    return {"neighbors": int(o["mesh_neighbors"])}
+
+
 def _boundary_params(o: dict) -> dict:
     check_boundary_dir(o["boundary_dir"])
     return {"dir": o["boundary_dir"], "scores": []}
@@ -826,6 +881,8 @@ STAGES = (
           _queue_floor, _write_floorplan),
     Stage("mesh", "clean", lambda o: o["mesh_points"], _mesh_params, ("_oriented.ply", "_oriented.json"),
           _queue_mesh, _write_oriented),
+    Stage("trimesh", "mesh", lambda o: o["simple_mesh"], _trimesh_params, ("_mesh.ply", "_mesh.json"),
+          _queue_trimesh, _write_trimesh),
     Stage("boundary", None, lambda o: o["boundary_dir"] is not None, _boundary_params, ("_boundary.json",),
           _boundary, _write_boundary, _report_boundary),
 )
@@ -888,6 +945,12 @@ def main():
                         help="Voxel edge of --mesh_points in metres (default 0.05); normals use radius 2 * voxel_size")
     parser.add_argument("--normals_max_nn", type=int, default=30,
                         help=f"Neighbours at the most per normal (1..{PC.MAX_NN}, default 30)")
+    # the two options below are passed on only when given: a run without them passes the keywords it always passed
+    parser.add_argument("--simple_mesh", action="store_true", default=argparse.SUPPRESS,
+                        help="Mesh the voxels of --mesh_points (which it implies) as the reference's --mesh_method simple "
+                             "does: nearest neighbours, a fan of triangles, clean-up; {frame}_mesh.ply and {frame}_mesh.json")
+    parser.add_argument("--mesh_neighbors", type=int, default=argparse.SUPPRESS,
+                        help=f"Nearest neighbours per vertex of --simple_mesh (2..{PC.MAX_K}, default 6)")
     parser.add_argument("--floor_plan", action="store_true",
                         help="Write the occupancy floor plan of the cleaned cloud (implies --clean_pointcloud): top-down "
                              "grid, closing and opening, connected regions; {frame}_floorplan.png and {frame}_floorplan.json")
@@ -902,7 +965,8 @@ def main():
     parser.add_argument("--resume", action="store_true",
                         help="Skip frames whose {frame}_depth.png (with --clean_pointcloud: and {frame}_clean.ply; with "
                              "--cluster_pointcloud: and {frame}_clusters.json; with --fit_shapes: and {frame}_shapes.json; with "
-                             "--mesh_points: and {frame}_oriented.ply / .json; with --floor_plan: and {frame}_floorplan.png / .json; with "
+                             "--mesh_points: and {frame}_oriented.ply / .json; with --simple_mesh: and {frame}_mesh.ply / .json; "
+                             "with --floor_plan: and {frame}_floorplan.png / .json; with "
                              "--boundary_dir, for a frame with a target: and {frame}_boundary.json) already exists in --output_dir")
     parser.add_argument("--colormap", type=str, default="turbo",
                         choices=["turbo", "viridis", "plasma", "inferno", "magma", "cividis", "jet"],
@@ -917,7 +981,9 @@ def main():
         check_stray(args.stray_radius, args.stray_neighbors)         # these, whether their stage is on or not
         check_cluster(args.cluster_eps, args.cluster_min_samples, args.cluster_max_points)
         check_circularity(args.circularity_threshold)
-        resolve_stages(**kw)                                         # and every stage that is on
+        if "mesh_neighbors" in kw:
+            check_mesh_neighbors(kw["mesh_neighbors"])
+        resolve_stages(**kw)                                        # and every stage that is on
     except ValueError as e:
         parser.error(str(e))
     batch_generate_depth_maps(**kw)

@@ -4,7 +4,7 @@
 // so each product and sum is rounded on its own.  Three kernels per sort pass (histogram, table
 // scan, scatter); no kernel waits on another workgroup's progress.
 #include "dp_common.h"
-#include "dp_points.h"
+#include "dp_grid3.h"
 
 #pragma clang fp contract(off)
 
@@ -13,18 +13,18 @@ namespace {
 constexpr int GRID_CAP = 4096;                  // workgroups of a per-point kernel at the most
 constexpr int SORT_ITEMS = 16;                  // rounds of 256 consecutive elements per workgroup
 constexpr int SORT_TILE = 256 * SORT_ITEMS;     // elements of one workgroup (sort)
-constexpr int CELL_BITS = 21;                   // stray grid: bits per axis of the packed cell key
-constexpr int CELL_MAX = (1 << CELL_BITS) - 2;  // largest cell coordinate (its +1 neighbour still fits)
 constexpr uint32_t NO_COL = 0xffffffffu;        // shadow stage: "in no column"
 
 struct Hdr {
-  u64 mm[6];            // keys of min / max of x, y, z over the finite points
-  uint32_t ctr[16];
-  double par[8];
+  Grid3 g;              // the stray stage's grid (dp_grid3.h); the shadow stage reads its extremes and finite count
+  uint32_t ctr[8];
+  double par[4];        // shadow stage: first x edge, first z edge, cell size; [3] is padding for tot
   uint32_t tot[8][256]; // per sort pass: elements per digit (all workgroups)
 };
-enum { C_FINITE = 0, C_NONFINITE = 1, C_KEPT = 2, C_ERR = 3, C_OCC = 4, C_TESTED = 5, C_REMCOL = 6, C_REMPTS = 7,
-       C_LENX = 8, C_LENZ = 9 };
+// run_sort clears tot with a memset; 8 bytes off a 16-byte boundary every sort took about 4 us longer
+// (profiles/grid3_shared/speed.md)
+static_assert(offsetof(Hdr, tot) % 16 == 0, "keep tot on a 16-byte boundary");
+enum { C_KEPT = 0, C_SHADOW_ERR = 1, C_OCC = 2, C_TESTED = 3, C_REMCOL = 4, C_REMPTS = 5, C_LENX = 6, C_LENZ = 7 };
 
 __device__ __forceinline__ u64 lanes_below() { return (1ull << (threadIdx.x & 63)) - 1ull; }
 
@@ -191,89 +191,19 @@ bool ws_carve(void* ws, int64_t bytes, int n_max, Ws* o) {
   return true;
 }
 
-// ---- shared by the two stages -------------------------------------------------------------------
-__global__ void hdr_init_kernel(Hdr* h) {
-  for (int a = 0; a < 3; ++a) { h->mm[2 * a] = ~0ull; h->mm[2 * a + 1] = 0; }
-}
-
-__global__ void __launch_bounds__(256) minmax3_kernel(const double* __restrict__ pts, const int32_t* n_dev, int n_max,
-                                                      Hdr* h) {
-  const int n = live_n(n_dev, n_max);
-  u64 mn[3] = {~0ull, ~0ull, ~0ull}, mx[3] = {0, 0, 0};
-  uint32_t bad = 0, good = 0;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    const double x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
-    if (!finite3(x, y, z)) { ++bad; continue; }
-    ++good;
-    const u64 k[3] = {okey(x), okey(y), okey(z)};
-    #pragma unroll
-    for (int a = 0; a < 3; ++a) { mn[a] = k[a] < mn[a] ? k[a] : mn[a]; mx[a] = k[a] > mx[a] ? k[a] : mx[a]; }
-  }
-  #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    wave_minmax(mn, mx, o);
-    bad += __shfl_xor(bad, o);
-    good += __shfl_xor(good, o);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    if (good) {
-      flush_minmax(h->mm, mn, mx);
-      atomicAdd(&h->ctr[C_FINITE], good);
-    }
-    if (bad) atomicAdd(&h->ctr[C_NONFINITE], bad);
-  }
-}
+// ---- shared by the two stages: this, and minmax3_kernel of dp_grid3.h ----------------------------
+__global__ void hdr_init_kernel(Hdr* h) { grid3_reset(&h->g); }
 
 // ---- stray points -------------------------------------------------------------------------------
-// Cell edge = radius * (1 + 2^-20), cell = floor((p - min) / edge) per axis.  Why the 3 x 3 x 3 cells
-// around a point hold every true neighbour: for |xi - xj| < radius the exact quotients differ by less
-// than 1 / (1 + 2^-20) < 1 - 2^-21; the computed quotient (a subtraction, a division and the edge
-// itself, each rounded once) is within 2^-50 relative of the exact one and below 2^21, so within
-// 2^-29 absolute; the computed quotients therefore differ by less than 1 and their floors by at most
-// 1.  Cells only select candidates: the distance test runs on the original coordinates.
-__global__ void stray_setup_kernel(Hdr* h, double radius) {
-  const double edge = radius * (1.0 + 1.0 / 1048576.0);
-  bool err = false;
-  for (int a = 0; a < 3; ++a) {
-    const double mn = h->ctr[C_FINITE] ? unkey(h->mm[2 * a]) : 0.0, mx = h->ctr[C_FINITE] ? unkey(h->mm[2 * a + 1]) : 0.0;
-    h->par[a] = mn;
-    if (!((mx - mn) / edge < (double)CELL_MAX)) err = true;      // also catches an overflowing extent
-  }
-  h->par[3] = edge;
-  h->ctr[C_ERR] = err;
-}
-
-__device__ __forceinline__ u64 pack_cell(u64 cx, u64 cy, u64 cz) { return (cx << (2 * CELL_BITS)) | (cy << CELL_BITS) | cz; }
-
-__global__ void __launch_bounds__(256) stray_key_kernel(const double* __restrict__ pts, const int32_t* n_dev, int n_max,
-                                                        const Hdr* h, u64* __restrict__ keys, uint32_t* __restrict__ vals) {
-  const int n = live_n(n_dev, n_max);
-  const double mx = h->par[0], my = h->par[1], mz = h->par[2], edge = h->par[3];
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    const double x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
-    keys[i] = finite3(x, y, z) ? pack_cell(cell_of<CELL_MAX>(x, mx, edge), cell_of<CELL_MAX>(y, my, edge),
-                                           cell_of<CELL_MAX>(z, mz, edge))
-                               : ~0ull;
-    vals[i] = (uint32_t)i;
-  }
-}
-
-__global__ void __launch_bounds__(256) gather_points_kernel(const double* __restrict__ pts, const uint32_t* __restrict__ idx,
-                                                            const int32_t* n_dev, int n_max, double* __restrict__ out) {
-  const int n = live_n(n_dev, n_max);
-  for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < n; t += (long long)gridDim.x * 256) {
-    const size_t i = row_of(idx[t], n);
-    out[3 * t] = pts[3 * i]; out[3 * t + 1] = pts[3 * i + 1]; out[3 * t + 2] = pts[3 * i + 2];
-  }
-}
-
+// The grid (cell edge radius * EDGE_SLACK, keys, gathered coordinates) is dp_grid3.h's, and so is the
+// argument why the 3 x 3 x 3 cells around a point hold every true neighbour.
 // One thread per point, in sorted (cell) order.  Own (x, y) cell row first; every row's three
 // z-adjacent cells are one key range.  Stops at nb_points.
 __global__ void __launch_bounds__(256) stray_count_kernel(const u64* __restrict__ keys, const uint32_t* __restrict__ idx,
                                                           const double* __restrict__ sp, const int32_t* n_dev, int n_max,
                                                           double r2, int nb, Hdr* h, uint8_t* __restrict__ keep) {
   const int n = live_n(n_dev, n_max);
-  const bool err = h->ctr[C_ERR] != 0;
+  const bool err = h->g.err != 0;
   for (long long base = (long long)blockIdx.x * 256; base < n; base += (long long)gridDim.x * 256) {
     const long long t = base + threadIdx.x;
     bool kept = false;
@@ -281,19 +211,18 @@ __global__ void __launch_bounds__(256) stray_count_kernel(const u64* __restrict_
       const u64 key = keys[t];
       if (err) {
         kept = true;
-      } else if (key != ~0ull) {
-        const long long cx = (long long)(key >> (2 * CELL_BITS)), cy = (long long)((key >> CELL_BITS) & ((1 << CELL_BITS) - 1)),
-                        cz = (long long)(key & ((1 << CELL_BITS) - 1));
+      } else if (key != NO_KEY) {
+        int cx, cy, cz;
+        unpack_cell(key, cx, cy, cz);
         const double x = sp[3 * t], y = sp[3 * t + 1], z = sp[3 * t + 2];
-        const u64 zlo = (u64)(cz > 0 ? cz - 1 : 0), zhi = (u64)(cz + 1);
         int cnt = 0;
         for (int row = 0; row < 9 && cnt < nb; ++row) {
           // row 0 is (0, 0); the others follow in any fixed order
           const int rr = row == 0 ? 4 : (row <= 4 ? row - 1 : row);
-          const long long rx = cx + rr / 3 - 1, ry = cy + rr % 3 - 1;
+          const int rx = cx + rr / 3 - 1, ry = cy + rr % 3 - 1;
           if (rx < 0 || ry < 0 || rx > CELL_MAX + 1 || ry > CELL_MAX + 1) continue;
-          const int a = lower_bound(keys, n, pack_cell((u64)rx, (u64)ry, zlo));
-          const int b = lower_bound(keys, n, pack_cell((u64)rx, (u64)ry, zhi) + 1);
+          int a, b;
+          cell_row_range(keys, n, rx, ry, cz > 0 ? cz - 1 : 0, cz + 1, a, b);
           for (int c = a; c < b && cnt < nb; ++c) {
             const double dx = sp[3 * (size_t)c] - x, dy = sp[3 * (size_t)c + 1] - y, dz = sp[3 * (size_t)c + 2] - z;
             if ((dx * dx + dy * dy) + dz * dz < r2) ++cnt;
@@ -309,11 +238,11 @@ __global__ void __launch_bounds__(256) stray_count_kernel(const u64* __restrict_
 
 __global__ void stray_final_kernel(const Hdr* h, const int32_t* n_dev, int n_max, double* st) {
   const int n = live_n(n_dev, n_max);
-  st[0] = (double)h->ctr[C_FINITE];
-  st[1] = (double)h->ctr[C_NONFINITE];
+  st[0] = (double)h->g.finite;
+  st[1] = (double)h->g.nonfinite;
   st[2] = (double)h->ctr[C_KEPT];
   st[3] = (double)(n - (int)h->ctr[C_KEPT]);
-  st[4] = (double)h->ctr[C_ERR];
+  st[4] = (double)h->g.err;
   st[5] = st[6] = st[7] = 0.0;
 }
 
@@ -343,11 +272,11 @@ __device__ __forceinline__ Bins bins_of(const Hdr* h, int axis) {   // axis 0: x
 }
 
 __global__ void shadow_setup_kernel(Hdr* h) {
-  const uint32_t nf = h->ctr[C_FINITE];
+  const uint32_t nf = h->g.finite;
   double cell = 0.05;
   uint32_t lx = 0, lz = 0, err = 0;
   if (nf) {
-    const double x0 = unkey(h->mm[0]), x1 = unkey(h->mm[1]), z0 = unkey(h->mm[4]), z1 = unkey(h->mm[5]);
+    const double x0 = unkey(h->g.mm[0]), x1 = unkey(h->g.mm[1]), z0 = unkey(h->g.mm[4]), z1 = unkey(h->g.mm[5]);
     const double density = (double)nf / ((x1 - x0) * (z1 - z0));
     const double v = 1.0 / __builtin_sqrt(density / 10.0);
     cell = v > 0.05 ? v : 0.05;                     // Python's max(0.05, v): 0.05 unless v > 0.05 (NaN included)
@@ -365,7 +294,7 @@ __global__ void shadow_setup_kernel(Hdr* h) {
   h->par[2] = cell;
   h->ctr[C_LENX] = lx;
   h->ctr[C_LENZ] = lz;
-  h->ctr[C_ERR] = err;
+  h->ctr[C_SHADOW_ERR] = err;
 }
 
 __global__ void __launch_bounds__(256) shadow_ykey_kernel(const double* __restrict__ pts, const int32_t* n_dev, int n_max,
@@ -383,7 +312,7 @@ __global__ void __launch_bounds__(256) shadow_colkey_kernel(const double* __rest
                                                             const int32_t* n_dev, int n_max, const Hdr* h,
                                                             u64* __restrict__ keys) {
   const int n = live_n(n_dev, n_max);
-  const bool err = h->ctr[C_ERR] != 0;
+  const bool err = h->ctr[C_SHADOW_ERR] != 0;
   const Bins bx = bins_of(h, 0), bz = bins_of(h, 1);
   for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < n; t += (long long)gridDim.x * 256) {
     const size_t i = row_of(idx[t], n);
@@ -506,14 +435,14 @@ __global__ void __launch_bounds__(256) shadow_mark_kernel(const u64* __restrict_
 }
 
 __global__ void shadow_final_kernel(const Hdr* h, double* st) {
-  st[0] = (double)h->ctr[C_FINITE];
-  st[1] = (double)h->ctr[C_NONFINITE];
+  st[0] = (double)h->g.finite;
+  st[1] = (double)h->g.nonfinite;
   st[2] = (double)h->ctr[C_OCC];
   st[3] = (double)h->ctr[C_TESTED];
   st[4] = (double)h->ctr[C_REMCOL];
   st[5] = (double)h->ctr[C_REMPTS];
   st[6] = h->par[2];
-  st[7] = (double)h->ctr[C_ERR];
+  st[7] = (double)h->ctr[C_SHADOW_ERR];
 }
 
 // ---- compaction ---------------------------------------------------------------------------------
@@ -572,9 +501,7 @@ extern "C" int dp_clean_stray(const double* points, const int32_t* n_dev, int32_
   double* sp = (double*)w.aux;
   (void)hipMemsetAsync(w.h, 0, sizeof(Hdr), s);
   hipLaunchKernelGGL(hdr_init_kernel, dim3(1), dim3(1), 0, s, w.h);
-  hipLaunchKernelGGL(minmax3_kernel, dim3(g), dim3(256), 0, s, points, n_dev, n_max, w.h);
-  hipLaunchKernelGGL(stray_setup_kernel, dim3(1), dim3(1), 0, s, w.h, radius);
-  hipLaunchKernelGGL(stray_key_kernel, dim3(g), dim3(256), 0, s, points, n_dev, n_max, w.h, w.ka, w.va);
+  grid3_keys(s, &w.h->g, g, points, n_dev, n_max, radius * EDGE_SLACK, 0.0, w.ka, w.va);
   const bool in_b = run_sort(s, w.h, w.ka, w.va, w.kb, w.vb, w.table, n_dev, n_max, 0, 64);
   const u64* sk = in_b ? w.kb : w.ka;
   const uint32_t* si = in_b ? w.vb : w.va;
@@ -599,7 +526,7 @@ extern "C" int dp_clean_shadows(const double* points, const int32_t* n_dev, int3
   uint32_t* head_of = (uint32_t*)(w.aux + al256(8 * (int64_t)n_max));
   (void)hipMemsetAsync(w.h, 0, sizeof(Hdr), s);
   hipLaunchKernelGGL(hdr_init_kernel, dim3(1), dim3(1), 0, s, w.h);
-  hipLaunchKernelGGL(minmax3_kernel, dim3(g), dim3(256), 0, s, points, n_dev, n_max, w.h);
+  hipLaunchKernelGGL(minmax3_kernel, dim3(g), dim3(256), 0, s, points, n_dev, n_max, &w.h->g);
   hipLaunchKernelGGL(shadow_setup_kernel, dim3(1), dim3(1), 0, s, w.h);
   hipLaunchKernelGGL(shadow_ykey_kernel, dim3(g), dim3(256), 0, s, points, n_dev, n_max, w.ka, w.va);
   // by y (64 bits), then by column id (32 bits): the second sort is stable, so a column's run is in
@@ -628,7 +555,7 @@ extern "C" int dp_compact_points(const double* points, const uint8_t* colors, co
   Ws w;
   if (!ws_carve(workspace, workspace_bytes, n_max, &w)) return DP_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const int nb = (int)(((int64_t)n_max + SCAN_TILE - 1) / SCAN_TILE);
+  const int nb = (int)scan_blocks_for(n_max);
   uint32_t* bc = w.va;                                            // n / 2048 words
   if (nb) hipLaunchKernelGGL(scan_count_kernel, dim3(nb), dim3(256), 0, s, keep, n_dev, n_max, bc);
   hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(256), 0, s, bc, nb, (uint32_t*)n_out_dev);   // the same bits

@@ -446,7 +446,6 @@ __global__ void __launch_bounds__(256) tfinal_kernel(const int32_t* ncl, int max
   }
 }
 
-int scan_blocks(int64_t n_max) { return (int)((n_max + SCAN_TILE - 1) / SCAN_TILE); }
 
 // ---- workspace ----------------------------------------------------------------------------------
 struct Ws {
@@ -462,7 +461,7 @@ struct Ws {
 int64_t ws_bytes_for(int64_t n_max) {
   const int64_t n = n_max < 0 ? 0 : n_max;
   return al256(sizeof(CHdr)) + al256(dp_clean_workspace_size(n)) + al256(8 * n) + 2 * al256(8 * n) + 6 * al256(4 * n) +
-         al256(4 * (int64_t)scan_blocks(n)) + 3 * al256(n) + 256;
+         al256(4 * scan_blocks_for(n)) + 3 * al256(n) + 256;
 }
 bool ws_carve(void* ws, int64_t bytes, int n_max, Ws* o) {
   if (!ws || bytes < ws_bytes_for(n_max) || ((uintptr_t)ws & 7)) return false;
@@ -480,7 +479,7 @@ bool ws_carve(void* ws, int64_t bytes, int n_max, Ws* o) {
   o->cend = (uint32_t*)p;     p += al256(4 * n);
   o->parent = (uint32_t*)p;   p += al256(4 * n);
   o->rank = (uint32_t*)p;     p += al256(4 * n);
-  o->bc = (uint32_t*)p;       p += al256(4 * (int64_t)scan_blocks(n));
+  o->bc = (uint32_t*)p;       p += al256(4 * scan_blocks_for(n));
   o->part = (uint8_t*)p;      p += al256(n);
   o->core = (uint8_t*)p;      p += al256(n);
   o->rootf = (uint8_t*)p;
@@ -489,7 +488,7 @@ bool ws_carve(void* ws, int64_t bytes, int n_max, Ws* o) {
 
 // exclusive scan of f (bytes, row order) into out, the total into *tot
 void run_scan(hipStream_t s, const Ws& w, const uint8_t* f, const int32_t* n_dev, int n_max, uint32_t* out, uint32_t* tot) {
-  const int nb = scan_blocks(n_max);
+  const int nb = (int)scan_blocks_for(n_max);
   if (nb) hipLaunchKernelGGL(scan_count_kernel, dim3(nb), dim3(256), 0, s, f, n_dev, n_max, w.bc);
   hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(256), 0, s, w.bc, nb, tot);
   if (nb) hipLaunchKernelGGL(scan_write_kernel, dim3(nb), dim3(256), 0, s, f, n_dev, n_max, w.bc, out);

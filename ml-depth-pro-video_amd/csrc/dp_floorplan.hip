@@ -466,7 +466,6 @@ struct Ws {
   uint8_t* flag;
   uint32_t* bc;
 };
-int64_t scan_blocks_for(int64_t n) { return (n + SCAN_TILE - 1) / SCAN_TILE; }
 // words of a packed grid: H * ceil(W / 64) <= (H W + 63 H) / 64
 int64_t bit_words_for(int64_t cells) { return cells / 64 + MAX_DIM + 1; }
 int64_t ws_bytes_for(int64_t max_cells, int64_t max_regions) {

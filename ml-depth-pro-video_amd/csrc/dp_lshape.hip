@@ -53,11 +53,10 @@ struct Ws {
   double* sub;
 };
 __host__ __device__ inline int64_t comps_for(int64_t cells) { return cells / 6 + 1; }
-int64_t tiles_for(int64_t cells) { return (cells + SCAN_TILE - 1) / SCAN_TILE; }
 int64_t ws_bytes_for(int64_t max_rects, int64_t max_cells) {
   const int64_t r = max_rects < 0 ? 0 : max_rects, c = max_cells < 0 ? 0 : max_cells;
   return al256(sizeof(LHdr)) + al256((int64_t)sizeof(Cand) * r) + 4 * al256(4 * (r + 1)) + 3 * al256(4 * r) + 4 * al256(c) +
-         4 * al256(4 * c) + al256(4 * (tiles_for(c) + 1)) + al256(4 * comps_for(c)) + al256(48 * comps_for(c)) + 256;
+         4 * al256(4 * c) + al256(4 * (scan_blocks_for(c) + 1)) + al256(4 * comps_for(c)) + al256(48 * comps_for(c)) + 256;
 }
 bool ws_carve(void* ws, int64_t bytes, int64_t r, int64_t c, Ws* o) {
   if (!ws || bytes < ws_bytes_for(r, c) || ((uintptr_t)ws & 7)) return false;
@@ -79,7 +78,7 @@ bool ws_carve(void* ws, int64_t bytes, int64_t r, int64_t c, Ws* o) {
   o->par2 = (uint32_t*)p;      p += al256(4 * c);
   o->sz1 = (uint32_t*)p;       p += al256(4 * c);
   o->sz2 = (uint32_t*)p;       p += al256(4 * c);
-  o->bc = (uint32_t*)p;        p += al256(4 * (tiles_for(c) + 1));
+  o->bc = (uint32_t*)p;        p += al256(4 * (scan_blocks_for(c) + 1));
   o->croot = (uint32_t*)p;     p += al256(4 * comps_for(c));
   o->sub = (double*)p;
   return true;
@@ -529,7 +528,7 @@ extern "C" int dp_lshape_split(const double* points, const int32_t* labels, cons
   Ws w;
   if (!ws_carve(workspace, workspace_bytes, max_rects, max_cells, &w)) return DP_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const int gc = grid_for(max_cells, GRID_CAP), nb = (int)tiles_for(max_cells);
+  const int gc = grid_for(max_cells, GRID_CAP), nb = (int)scan_blocks_for(max_cells);
   hipLaunchKernelGGL(prep_kernel, dim3(1), dim3(NT), 0, s, rects, n_rects_dev, max_rects, max_cells, w);
   if (max_cells > 0) {
     hipError_t e = hipMemsetAsync(w.b, 0, (size_t)max_cells, s);

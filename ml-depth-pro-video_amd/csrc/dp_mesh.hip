@@ -3,119 +3,33 @@
 // and duplicated triangles (dp_mesh_clean_triangles), plus the mean neighbour distance of a list
 // (dp_mesh_mean_distance).  pointcloud_to_mesh.py:397-465.  The specification is in dp_mi355x.h.  fp64, no FMA
 // contraction anywhere in this file.  The grid is dp_knn_search's (cell keys, dp_sort_pairs, cell rows by
-// binary search); its five small set-up kernels are restated here, so that dp_normals.hip is built as it was.
+// binary search, the top-k merge): it lives in dp_grid3.h.
 #include "dp_common.h"
-#include "dp_points.h"
+#include "dp_grid3.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
 constexpr int GRID_CAP = 4096;                  // workgroups of a per-row kernel at the most
-constexpr int CELL_BITS = 21;                   // bits per axis of the packed cell key
-constexpr int CELL_MAX = (1 << CELL_BITS) - 2;  // largest cell coordinate (its +1 neighbour still fits)
-constexpr u64 NO_KEY = ~0ull;                   // key of a row that takes no part (sorts last)
 constexpr int MAX_K = 64;                       // one kept neighbour per lane
 constexpr int RING_MAX = 8;                     // rings walked cell by cell; a query that needs more reads every row
 
 struct Hdr {
-  u64 mm[6];            // keys of min / max of x, y, z over the finite points
-  uint32_t ctr[8];
-  int32_t ext[4];       // largest cell coordinate per axis
-  double par[8];        // origin x, y, z, the grid's cell edge
+  Grid3 g;              // dp_knn_exact
+  uint32_t ctr[5];
 };
-enum { C_FINITE = 0, C_NONFINITE = 1, C_ERR = 2, C_FEW = 3, C_RING = 4,           // dp_knn_exact
-       T_INVALID = 1, T_DEGENERATE = 2, T_HEADS = 3 };                              // dp_mesh_clean_triangles
+enum { C_FEW = 0, C_RING = 1,                                                       // dp_knn_exact
+       T_INVALID = 2, T_DEGENERATE = 3, T_HEADS = 4 };                              // dp_mesh_clean_triangles
 
 __global__ void hdr_init_kernel(Hdr* h) {
-  for (int a = 0; a < 3; ++a) { h->mm[2 * a] = ~0ull; h->mm[2 * a + 1] = 0; }
-  for (int a = 0; a < 8; ++a) { h->ctr[a] = 0; h->par[a] = 0.0; }
-  for (int a = 0; a < 4; ++a) h->ext[a] = 0;
-}
-
-__global__ void __launch_bounds__(256) minmax3_kernel(const double* __restrict__ pts, const int32_t* n_dev, int n_max,
-                                                      Hdr* h) {
-  const int n = live_n(n_dev, n_max);
-  u64 mn[3] = {~0ull, ~0ull, ~0ull}, mx[3] = {0, 0, 0};
-  uint32_t bad = 0, good = 0;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    const double x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
-    if (!finite3(x, y, z)) { ++bad; continue; }
-    ++good;
-    const u64 k[3] = {okey(x), okey(y), okey(z)};
-    #pragma unroll
-    for (int a = 0; a < 3; ++a) { mn[a] = k[a] < mn[a] ? k[a] : mn[a]; mx[a] = k[a] > mx[a] ? k[a] : mx[a]; }
-  }
-  #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    wave_minmax(mn, mx, o);
-    bad += __shfl_xor(bad, o);
-    good += __shfl_xor(good, o);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    if (good) {
-      flush_minmax(h->mm, mn, mx);
-      atomicAdd(&h->ctr[C_FINITE], good);
-    }
-    if (bad) atomicAdd(&h->ctr[C_NONFINITE], bad);
-  }
-}
-
-// origin = the minimum per axis; the largest cell per axis; the error flag if an axis needs more than CELL_MAX cells
-__global__ void grid_setup_kernel(Hdr* h, double edge) {
-  bool err = false;
-  for (int a = 0; a < 3; ++a) {
-    const double mn = h->ctr[C_FINITE] ? unkey(h->mm[2 * a]) : 0.0, mx = h->ctr[C_FINITE] ? unkey(h->mm[2 * a + 1]) : 0.0;
-    h->par[a] = mn;
-    if (!((mx - mn) / edge < (double)CELL_MAX)) err = true;       // also catches an overflowing extent
-    h->ext[a] = (int32_t)cell_of<CELL_MAX>(mx, mn, edge);
-  }
-  h->par[3] = edge;
-  h->ctr[C_ERR] = err;
-}
-
-__device__ __forceinline__ u64 pack_cell(u64 cx, u64 cy, u64 cz) { return (cx << (2 * CELL_BITS)) | (cy << CELL_BITS) | cz; }
-
-// With the error flag up every row gets NO_KEY: no query then has a list.
-__global__ void __launch_bounds__(256) cell_key_kernel(const double* __restrict__ pts, const int32_t* n_dev, int n_max,
-                                                       const Hdr* h, u64* __restrict__ keys, uint32_t* __restrict__ vals) {
-  const int n = live_n(n_dev, n_max);
-  const double ox = h->par[0], oy = h->par[1], oz = h->par[2], edge = h->par[3];
-  const bool err = h->ctr[C_ERR] != 0;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    const double x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
-    keys[i] = !err && finite3(x, y, z) ? pack_cell(cell_of<CELL_MAX>(x, ox, edge), cell_of<CELL_MAX>(y, oy, edge),
-                                                   cell_of<CELL_MAX>(z, oz, edge))
-                                       : NO_KEY;
-    vals[i] = (uint32_t)i;
-  }
-}
-
-__global__ void __launch_bounds__(256) gather_points_kernel(const double* __restrict__ pts, const uint32_t* __restrict__ idx,
-                                                            const int32_t* n_dev, int n_max, double* __restrict__ out) {
-  const int n = live_n(n_dev, n_max);
-  for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < n; t += (long long)gridDim.x * 256) {
-    const size_t i = row_of(idx[t], n);
-    out[3 * t] = pts[3 * i]; out[3 * t + 1] = pts[3 * i + 1]; out[3 * t + 2] = pts[3 * i + 2];
-  }
+  grid3_reset(&h->g);
+  for (int a = 0; a < 5; ++a) h->ctr[a] = 0;
 }
 
 // ---- exact k nearest ------------------------------------------------------------------------------
-// (d2 bits, row) pairs, compared as the pair: d2 >= +0.0, so its bit pattern orders as the value does
-__device__ __forceinline__ bool pair_less(u64 ka, uint32_t ra, u64 kb, uint32_t rb) { return ka < kb || (ka == kb && ra < rb); }
-
-// compare-exchange with lane ^ j; keep_min says which of the two this lane keeps
-__device__ __forceinline__ void cmp_xchg(u64& k, uint32_t& r, int j, bool keep_min) {
-  const u64 ok = __shfl_xor(k, j);
-  const uint32_t orr = __shfl_xor(r, j);
-  const bool other_less = pair_less(ok, orr, k, r);
-  if (other_less == keep_min) { k = ok; r = orr; }
-}
-
-// Lane l offers the sorted position c (live: c is a candidate, never the query itself).  A batch holding a
-// candidate below the current k-th smallest is sorted across the lanes (bitonic, shuffles) and merged with the
-// running best, held one per lane in ascending (d2, row) order: best[l] = min(best[l], batch[63 - l]) is bitonic
-// and holds the 64 smallest of the 128; six more steps sort it.  dp_knn_search's merge.
+// Lane l offers the sorted position c (live: c is a candidate, never the query itself) to the running best.
+// Called by all 64 lanes of the wave together.
 __device__ __forceinline__ void offer(bool live, int c, const double* __restrict__ sp, const uint32_t* __restrict__ idx,
                                       double x, double y, double z, int k, int lane, u64& bk, uint32_t& br) {
   u64 ck = NO_KEY;
@@ -126,22 +40,7 @@ __device__ __forceinline__ void offer(bool live, int c, const double* __restrict
     ck = (u64)__double_as_longlong(d2);
     cr = idx[c];
   }
-  // what is not below the current k-th smallest can never make the list
-  const u64 tk = __shfl(bk, k - 1);
-  const uint32_t tr = __shfl(br, k - 1);
-  const bool pass = live && pair_less(ck, cr, tk, tr);
-  if (!__ballot(pass)) return;
-  if (!pass) { ck = NO_KEY; cr = ~0u; }
-  #pragma unroll
-  for (int kk = 2; kk <= 64; kk <<= 1) {
-    #pragma unroll
-    for (int j = kk >> 1; j > 0; j >>= 1) cmp_xchg(ck, cr, j, ((lane & j) == 0) == ((lane & kk) == 0));
-  }
-  const u64 rk = __shfl(ck, 63 - lane);
-  const uint32_t rw = __shfl(cr, 63 - lane);
-  if (pair_less(rk, rw, bk, br)) { bk = rk; br = rw; }
-  #pragma unroll
-  for (int j = 32; j > 0; j >>= 1) cmp_xchg(bk, br, j, (lane & j) == 0);
+  wave_top64_merge(live, ck, cr, k, lane, bk, br);
 }
 
 // smallest r >= 0 with d2 < (r * edge) * (r * edge), capped at cap: rule 4's distance ring
@@ -161,17 +60,17 @@ __device__ __forceinline__ int ring_of(double d2, double edge, int cap) {
 // for the (2 r - 1)^2 rows inside it the two cells at cz - r and cz + r.  Each lane takes one range (its two
 // binary searches), clipped to the grid's extent; the ranges' candidates are numbered through a prefix sum over
 // the lanes and go 64 at a time to `offer`.  After ring r the walk ends if the list is full with its largest d2
-// below (r * cell_edge)^2 -- the grid's edge is cell_edge * (1 + 2^-20), so no unvisited cell holds a point that
-// near, the stray stage's argument -- or if the cube covers the grid.  A query still open after RING_MAX rings
-// starts again over every participant, in sorted order: bounded work whatever the cloud looks like.
+// below (r * cell_edge)^2 -- the grid's edge is cell_edge * EDGE_SLACK, so no unvisited cell holds a point that
+// near, the argument at EDGE_SLACK (dp_grid3.h) -- or if the cube covers the grid.  A query still open after
+// RING_MAX rings starts again over every participant, in sorted order: bounded work whatever the cloud looks like.
 __global__ void __launch_bounds__(256) knn_exact_kernel(const u64* __restrict__ keys, const uint32_t* __restrict__ idx,
                                                         const double* __restrict__ sp, const int32_t* n_dev, int n_max,
                                                         double edge, int k, Hdr* h, int32_t* __restrict__ nbr,
                                                         int32_t* __restrict__ nbr_count, double* __restrict__ d2_out) {
   const int n = live_n(n_dev, n_max), lane = threadIdx.x & 63;
-  const bool err = h->ctr[C_ERR] != 0;
-  const int nfin = err ? 0 : (int)(h->ctr[C_FINITE] < (uint32_t)n ? h->ctr[C_FINITE] : (uint32_t)n);
-  const int ex = h->ext[0], ey = h->ext[1], ez = h->ext[2];
+  const bool err = h->g.err != 0;
+  const int nfin = err ? 0 : (int)(h->g.finite < (uint32_t)n ? h->g.finite : (uint32_t)n);
+  const int ex = h->g.ext[0], ey = h->g.ext[1], ez = h->g.ext[2];
   uint32_t few = 0;                                       // this wave's counters (lane-uniform)
   int ring_max = 0;
   for (long long q = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); q < n; q += (long long)gridDim.x * 4) {
@@ -182,8 +81,8 @@ __global__ void __launch_bounds__(256) knn_exact_kernel(const u64* __restrict__ 
     uint32_t br = ~0u;
     uint32_t cnt = 0;
     if (key != NO_KEY && q < nfin) {
-      const int cx = (int)(key >> (2 * CELL_BITS)), cy = (int)((key >> CELL_BITS) & ((1 << CELL_BITS) - 1)),
-                cz = (int)(key & ((1 << CELL_BITS) - 1));
+      int cx, cy, cz;
+      unpack_cell(key, cx, cy, cz);
       const double x = sp[3 * q], y = sp[3 * q + 1], z = sp[3 * q + 2];
       int cover = cx > ex - cx ? cx : ex - cx;            // the ring at which the cube covers the grid
       cover = cy > cover ? cy : cover; cover = ey - cy > cover ? ey - cy : cover;
@@ -212,8 +111,8 @@ __global__ void __launch_bounds__(256) knn_exact_kernel(const u64* __restrict__ 
             zlo = zlo < 0 ? 0 : zlo;
             zhi = zhi > ez ? ez : zhi;
             if (rx >= 0 && rx <= ex && ry >= 0 && ry <= ey && zlo <= zhi) {
-              a = lower_bound(keys, nfin, pack_cell((u64)rx, (u64)ry, (u64)zlo));
-              const int b = lower_bound(keys, nfin, pack_cell((u64)rx, (u64)ry, (u64)zhi) + 1);
+              int b;
+              cell_row_range(keys, nfin, rx, ry, zlo, zhi, a, b);
               len = (uint32_t)(b - a);
             }
           }
@@ -268,12 +167,12 @@ __global__ void __launch_bounds__(256) knn_exact_kernel(const u64* __restrict__ 
 }
 
 __global__ void knn_exact_final_kernel(const Hdr* h, double* st) {
-  const bool err = h->ctr[C_ERR] != 0;
-  st[0] = (double)h->ctr[C_FINITE];
-  st[1] = (double)h->ctr[C_NONFINITE];
-  st[2] = err ? (double)h->ctr[C_FINITE] : (double)h->ctr[C_FEW];     // no list at all under the flag
+  const bool err = h->g.err != 0;
+  st[0] = (double)h->g.finite;
+  st[1] = (double)h->g.nonfinite;
+  st[2] = err ? (double)h->g.finite : (double)h->ctr[C_FEW];          // no list at all under the flag
   st[3] = (double)h->ctr[C_RING];
-  st[4] = (double)h->ctr[C_ERR];
+  st[4] = (double)h->g.err;
   st[5] = st[6] = st[7] = 0.0;
 }
 
@@ -432,7 +331,6 @@ struct Ws {
   void* sort;
   int64_t sort_bytes;
 };
-int64_t scan_blocks_for(int64_t n) { return (n + SCAN_TILE - 1) / SCAN_TILE; }
 int64_t clamp0(int64_t n) { return n < 0 ? 0 : n; }
 // keys, payloads, flags, block counts and the sort's own space for max(n, t) elements; coordinates for n rows
 int64_t ws_bytes_for(int64_t n_max, int64_t t_max) {
@@ -470,9 +368,7 @@ extern "C" int dp_knn_exact(const double* points, const int32_t* n_dev, int32_t 
   hipStream_t s = (hipStream_t)stream;
   const int g = grid_for(n_max, GRID_CAP);
   hipLaunchKernelGGL(hdr_init_kernel, dim3(1), dim3(1), 0, s, w.h);
-  hipLaunchKernelGGL(minmax3_kernel, dim3(g), dim3(256), 0, s, points, n_dev, n_max, w.h);
-  hipLaunchKernelGGL(grid_setup_kernel, dim3(1), dim3(1), 0, s, w.h, cell_edge * (1.0 + 1.0 / 1048576.0));
-  hipLaunchKernelGGL(cell_key_kernel, dim3(g), dim3(256), 0, s, points, n_dev, n_max, w.h, w.keys, w.vals);
+  grid3_keys(s, &w.h->g, g, points, n_dev, n_max, cell_edge * EDGE_SLACK, 0.0, w.keys, w.vals);
   const int rc = dp_sort_pairs((uint64_t*)w.keys, w.vals, n_dev, n_max, 0, 64, w.sort, w.sort_bytes, (dp_stream_t)s);
   if (rc) return rc;
   hipLaunchKernelGGL(gather_points_kernel, dim3(g), dim3(256), 0, s, points, w.vals, n_dev, n_max, w.sp);

@@ -1,89 +1,27 @@
 // Oriented mesh points (ABI 19): voxel-grid down-sampling, the hybrid (radius + max_nn) neighbour search
 // and PCA normals oriented towards a camera -- the three Open3D calls every meshing method of the
 // reference starts with (pointcloud_to_mesh.py:313-395).  The specification is in dp_mi355x.h.  fp64, no
-// FMA contraction anywhere in this file.  The grid (cell keys, dp_sort_pairs, cell starts by binary search)
-// is the stray stage's; the sort is called through its exported entry point, so dp_clean.hip is untouched.
+// FMA contraction anywhere in this file.  The grid (cell keys, cell rows by binary search, the top-k merge)
+// is dp_grid3.h's; the sort is dp_clean.hip's, called through its exported entry point dp_sort_pairs.
 #include "dp_common.h"
-#include "dp_points.h"
+#include "dp_grid3.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
 constexpr int GRID_CAP = 4096;                  // workgroups of a per-point kernel at the most
-constexpr int CELL_BITS = 21;                   // bits per axis of the packed cell key
-constexpr int CELL_MAX = (1 << CELL_BITS) - 2;  // largest cell coordinate (its +1 neighbour still fits)
-constexpr u64 NO_KEY = ~0ull;                   // key of a row that takes no part (sorts last)
 constexpr int MAX_NN = 64;                      // one kept neighbour per lane
 
 struct Hdr {
-  u64 mm[6];            // keys of min / max of x, y, z over the finite points
-  uint32_t ctr[8];
-  double par[8];        // origin x, y, z, cell edge
+  Grid3 g;
+  uint32_t ctr[2];
 };
-enum { C_FINITE = 0, C_NONFINITE = 1, C_ERR = 2, C_FEW = 3, C_TRUNC = 4 };
+enum { C_FEW = 0, C_TRUNC = 1 };
 
 __global__ void hdr_init_kernel(Hdr* h) {
-  for (int a = 0; a < 3; ++a) { h->mm[2 * a] = ~0ull; h->mm[2 * a + 1] = 0; }
-  for (int a = 0; a < 8; ++a) { h->ctr[a] = 0; h->par[a] = 0.0; }
-}
-
-__global__ void __launch_bounds__(256) minmax3_kernel(const double* __restrict__ pts, const int32_t* n_dev, int n_max,
-                                                      Hdr* h) {
-  const int n = live_n(n_dev, n_max);
-  u64 mn[3] = {~0ull, ~0ull, ~0ull}, mx[3] = {0, 0, 0};
-  uint32_t bad = 0, good = 0;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    const double x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
-    if (!finite3(x, y, z)) { ++bad; continue; }
-    ++good;
-    const u64 k[3] = {okey(x), okey(y), okey(z)};
-    #pragma unroll
-    for (int a = 0; a < 3; ++a) { mn[a] = k[a] < mn[a] ? k[a] : mn[a]; mx[a] = k[a] > mx[a] ? k[a] : mx[a]; }
-  }
-  #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    wave_minmax(mn, mx, o);
-    bad += __shfl_xor(bad, o);
-    good += __shfl_xor(good, o);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    if (good) {
-      flush_minmax(h->mm, mn, mx);
-      atomicAdd(&h->ctr[C_FINITE], good);
-    }
-    if (bad) atomicAdd(&h->ctr[C_NONFINITE], bad);
-  }
-}
-
-// origin = min - shift per axis; the error flag if an axis needs more than CELL_MAX cells of `edge`
-__global__ void grid_setup_kernel(Hdr* h, double edge, double shift) {
-  bool err = false;
-  for (int a = 0; a < 3; ++a) {
-    const double mn = h->ctr[C_FINITE] ? unkey(h->mm[2 * a]) : 0.0, mx = h->ctr[C_FINITE] ? unkey(h->mm[2 * a + 1]) : 0.0;
-    const double org = mn - shift;
-    h->par[a] = org;
-    if (!((mx - org) / edge < (double)CELL_MAX)) err = true;      // also catches an overflowing extent
-  }
-  h->par[3] = edge;
-  h->ctr[C_ERR] = err;
-}
-
-__device__ __forceinline__ u64 pack_cell(u64 cx, u64 cy, u64 cz) { return (cx << (2 * CELL_BITS)) | (cy << CELL_BITS) | cz; }
-
-// With the error flag up every row gets NO_KEY: the stages below then find no voxel and no neighbour.
-__global__ void __launch_bounds__(256) cell_key_kernel(const double* __restrict__ pts, const int32_t* n_dev, int n_max,
-                                                       const Hdr* h, u64* __restrict__ keys, uint32_t* __restrict__ vals) {
-  const int n = live_n(n_dev, n_max);
-  const double ox = h->par[0], oy = h->par[1], oz = h->par[2], edge = h->par[3];
-  const bool err = h->ctr[C_ERR] != 0;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    const double x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
-    keys[i] = !err && finite3(x, y, z) ? pack_cell(cell_of<CELL_MAX>(x, ox, edge), cell_of<CELL_MAX>(y, oy, edge),
-                                                   cell_of<CELL_MAX>(z, oz, edge))
-                                       : NO_KEY;
-    vals[i] = (uint32_t)i;
-  }
+  grid3_reset(&h->g);
+  h->ctr[C_FEW] = h->ctr[C_TRUNC] = 0;
 }
 
 // ---- voxel grid -----------------------------------------------------------------------------------
@@ -165,41 +103,19 @@ __global__ void __launch_bounds__(256) vox_reduce_kernel(const double* __restric
 }
 
 __global__ void vox_final_kernel(const Hdr* h, const int32_t* n_out_dev, double* st) {
-  st[0] = (double)h->ctr[C_FINITE];
-  st[1] = (double)h->ctr[C_NONFINITE];
+  st[0] = (double)h->g.finite;
+  st[1] = (double)h->g.nonfinite;
   st[2] = (double)*n_out_dev;
   st[3] = st[4] = 0.0;
-  st[5] = (double)h->ctr[C_ERR];
+  st[5] = (double)h->g.err;
   st[6] = st[7] = 0.0;
 }
 
 // ---- hybrid search --------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) gather_points_kernel(const double* __restrict__ pts, const uint32_t* __restrict__ idx,
-                                                            const int32_t* n_dev, int n_max, double* __restrict__ out) {
-  const int n = live_n(n_dev, n_max);
-  for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < n; t += (long long)gridDim.x * 256) {
-    const size_t i = row_of(idx[t], n);
-    out[3 * t] = pts[3 * i]; out[3 * t + 1] = pts[3 * i + 1]; out[3 * t + 2] = pts[3 * i + 2];
-  }
-}
-
-// (d2 bits, row) pairs, compared as the pair: d2 >= +0.0, so its bit pattern orders as the value does
-__device__ __forceinline__ bool pair_less(u64 ka, uint32_t ra, u64 kb, uint32_t rb) { return ka < kb || (ka == kb && ra < rb); }
-
-// compare-exchange with lane ^ j; keep_min says which of the two this lane keeps
-__device__ __forceinline__ void cmp_xchg(u64& k, uint32_t& r, int j, bool keep_min) {
-  const u64 ok = __shfl_xor(k, j);
-  const uint32_t orr = __shfl_xor(r, j);
-  const bool other_less = pair_less(ok, orr, k, r);
-  if (other_less == keep_min) { k = ok; r = orr; }
-}
-
-// One wave per query, in sorted (cell) order.  Cell edge radius * (1 + 2^-20): the 3 x 3 x 3 cells around a
-// point hold every true neighbour (the argument is the stray stage's, dp_clean.hip); a (x, y) cell row's
-// three z-adjacent cells are one key range.  Lanes stride a range's candidates in batches of 64; a batch
-// with a candidate that can still make the list is sorted across the lanes (bitonic, shuffles) and merged
-// with the running best, which is held one per lane in ascending (d2, row) order: best[l] = min(best[l],
-// batch[63 - l]) is bitonic and holds the 64 smallest of the 128; six more steps sort it.
+// One wave per query, in sorted (cell) order.  Cell edge radius * EDGE_SLACK: the 3 x 3 x 3 cells around a
+// point hold every true neighbour (the argument stands at EDGE_SLACK, dp_grid3.h); a (x, y) cell row's
+// three z-adjacent cells are one key range.  Lanes stride a range's candidates in batches of 64, and each
+// batch goes to wave_top64_merge with the running best, held one per lane in ascending (d2, row) order.
 __global__ void __launch_bounds__(256) knn_kernel(const u64* __restrict__ keys, const uint32_t* __restrict__ idx,
                                                   const double* __restrict__ sp, const int32_t* n_dev, int n_max,
                                                   double r2, int max_nn, Hdr* h, int32_t* __restrict__ nbr,
@@ -214,15 +130,14 @@ __global__ void __launch_bounds__(256) knn_kernel(const u64* __restrict__ keys, 
     uint32_t br = ~0u;
     uint32_t total = 0;
     if (key != NO_KEY) {
-      const long long cx = (long long)(key >> (2 * CELL_BITS)), cy = (long long)((key >> CELL_BITS) & ((1 << CELL_BITS) - 1)),
-                      cz = (long long)(key & ((1 << CELL_BITS) - 1));
+      int cx, cy, cz;
+      unpack_cell(key, cx, cy, cz);
       const double x = sp[3 * q], y = sp[3 * q + 1], z = sp[3 * q + 2];
-      const u64 zlo = (u64)(cz > 0 ? cz - 1 : 0), zhi = (u64)(cz + 1);
       for (int rr = 0; rr < 9; ++rr) {
-        const long long rx = cx + rr / 3 - 1, ry = cy + rr % 3 - 1;
+        const int rx = cx + rr / 3 - 1, ry = cy + rr % 3 - 1;
         if (rx < 0 || ry < 0 || rx > CELL_MAX + 1 || ry > CELL_MAX + 1) continue;
-        const int a = lower_bound(keys, n, pack_cell((u64)rx, (u64)ry, zlo));
-        const int b = lower_bound(keys, n, pack_cell((u64)rx, (u64)ry, zhi) + 1);
+        int a, b;
+        cell_row_range(keys, n, rx, ry, cz > 0 ? cz - 1 : 0, cz + 1, a, b);
         for (int base = a; base < b; base += 64) {
           const int c = base + lane;
           bool hit = false;
@@ -235,22 +150,7 @@ __global__ void __launch_bounds__(256) knn_kernel(const u64* __restrict__ keys, 
             if (hit) { ck = (u64)__double_as_longlong(d2); cr = idx[c]; }
           }
           total += (uint32_t)__popcll(__ballot(hit));
-          // what is not below the current max_nn-th smallest can never make the list
-          const u64 tk = __shfl(bk, max_nn - 1);
-          const uint32_t tr = __shfl(br, max_nn - 1);
-          const bool pass = hit && pair_less(ck, cr, tk, tr);
-          if (!__ballot(pass)) continue;
-          if (!pass) { ck = NO_KEY; cr = ~0u; }
-          #pragma unroll
-          for (int k = 2; k <= 64; k <<= 1) {
-            #pragma unroll
-            for (int j = k >> 1; j > 0; j >>= 1) cmp_xchg(ck, cr, j, ((lane & j) == 0) == ((lane & k) == 0));
-          }
-          const u64 rk = __shfl(ck, 63 - lane);
-          const uint32_t rw = __shfl(cr, 63 - lane);
-          if (pair_less(rk, rw, bk, br)) { bk = rk; br = rw; }
-          #pragma unroll
-          for (int j = 32; j > 0; j >>= 1) cmp_xchg(bk, br, j, (lane & j) == 0);
+          wave_top64_merge(hit, ck, cr, max_nn, lane, bk, br);      // q, rr and base are the wave's: uniform here
         }
       }
       few += total < 3u;
@@ -267,13 +167,13 @@ __global__ void __launch_bounds__(256) knn_kernel(const u64* __restrict__ keys, 
 }
 
 __global__ void knn_final_kernel(const Hdr* h, double* st) {
-  const bool err = h->ctr[C_ERR] != 0;
-  st[0] = (double)h->ctr[C_FINITE];
-  st[1] = (double)h->ctr[C_NONFINITE];
-  st[2] = err ? (double)h->ctr[C_FINITE] : (double)h->ctr[C_FEW];     // no neighbourhood at all under the flag
+  const bool err = h->g.err != 0;
+  st[0] = (double)h->g.finite;
+  st[1] = (double)h->g.nonfinite;
+  st[2] = err ? (double)h->g.finite : (double)h->ctr[C_FEW];          // no neighbourhood at all under the flag
   st[3] = (double)h->ctr[C_TRUNC];
   st[4] = 0.0;
-  st[5] = (double)h->ctr[C_ERR];
+  st[5] = (double)h->g.err;
   st[6] = st[7] = 0.0;
 }
 
@@ -391,7 +291,6 @@ struct Ws {
   void* sort;
   int64_t sort_bytes;
 };
-int64_t scan_blocks_for(int64_t n) { return (n + SCAN_TILE - 1) / SCAN_TILE; }
 int64_t ws_bytes_for(int64_t n_max) {
   const int64_t n = n_max < 0 ? 0 : n_max;
   return al256(sizeof(Hdr)) + al256(8 * n) + al256(4 * n) + al256(4 * (n + 1)) + al256(4 * (scan_blocks_for(n) + 1)) + al256(n) +
@@ -415,11 +314,8 @@ bool ws_carve(void* ws, int64_t bytes, int n_max, Ws* o) {
 
 // minimum / maximum, cell keys of edge `edge` from origin min - shift, sorted by (cell, row)
 int sorted_cells(hipStream_t s, const Ws& w, const double* points, const int32_t* n_dev, int n_max, double edge, double shift) {
-  const int g = grid_for(n_max, GRID_CAP);
   hipLaunchKernelGGL(hdr_init_kernel, dim3(1), dim3(1), 0, s, w.h);
-  hipLaunchKernelGGL(minmax3_kernel, dim3(g), dim3(256), 0, s, points, n_dev, n_max, w.h);
-  hipLaunchKernelGGL(grid_setup_kernel, dim3(1), dim3(1), 0, s, w.h, edge, shift);
-  hipLaunchKernelGGL(cell_key_kernel, dim3(g), dim3(256), 0, s, points, n_dev, n_max, w.h, w.keys, w.vals);
+  grid3_keys(s, &w.h->g, grid_for(n_max, GRID_CAP), points, n_dev, n_max, edge, shift, w.keys, w.vals);
   return dp_sort_pairs((uint64_t*)w.keys, w.vals, n_dev, n_max, 0, 64, w.sort, w.sort_bytes, (dp_stream_t)s);
 }
 
@@ -464,7 +360,7 @@ extern "C" int dp_knn_search(const double* points, const int32_t* n_dev, int32_t
   Ws w;
   if (!ws_carve(workspace, workspace_bytes, n_max, &w)) return DP_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const int rc = sorted_cells(s, w, points, n_dev, n_max, radius * (1.0 + 1.0 / 1048576.0), 0.0);
+  const int rc = sorted_cells(s, w, points, n_dev, n_max, radius * EDGE_SLACK, 0.0);
   if (rc) return rc;
   hipLaunchKernelGGL(gather_points_kernel, dim3(grid_for(n_max, GRID_CAP)), dim3(256), 0, s, points, w.vals, n_dev, n_max, w.sp);
   hipLaunchKernelGGL(knn_kernel, dim3(grid_for(64 * (int64_t)n_max, GRID_CAP)), dim3(256), 0, s, w.keys, w.vals, w.sp, n_dev,

@@ -1,8 +1,9 @@
 // What the point-cloud stages share (dp_ground.hip, dp_clean.hip, dp_cluster.hip, dp_shapes.hip,
-// dp_normals.hip, dp_floorplan.hip, dp_lshape.hip): one
+// dp_normals.hip, dp_floorplan.hip, dp_lshape.hip, dp_mesh.hip): one
 // copy of every device and host helper that two or more of them use.  A helper with one user stays in
 // its file.  Everything is in an anonymous namespace, so each translation unit has its own copy of the
-// two kernels below.
+// two kernels below.  The sorted 3-D cell grid of dp_clean.hip, dp_normals.hip and dp_mesh.hip, kernels
+// included, is in dp_grid3.h, which includes this header and which only those three include.
 // Floating-point contraction: every stage compiles with `#pragma clang fp contract(off)`, and the header
 // sets it as well, so the helpers are built as they were inside the stages wherever the include stands.
 // It is a header for files that want contraction off; cell_of (a subtraction feeding a division) has
@@ -318,6 +319,8 @@ __global__ void __launch_bounds__(256) scan_blocks_kernel(uint32_t* __restrict__
 
 // ---- host ----------------------------------------------------------------------------------------
 int64_t al256(int64_t b) { return (b + 255) / 256 * 256; }
+// workgroups of the flag scan (tiles of SCAN_TILE rows) for n rows
+int64_t scan_blocks_for(int64_t n) { return (n + SCAN_TILE - 1) / SCAN_TILE; }
 // workgroups of 256 threads for n elements in a grid-stride loop: at least one, at most cap
 int grid_for(int64_t n, int cap) {
   const int64_t g = (n + 255) / 256;

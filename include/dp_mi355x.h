@@ -96,6 +96,16 @@ int dp_abi_version(void);
  *   relu(sum_o head_w[o] * relu(v[q*32+o] - border(q, y, x, o)) + head_b), where border() sums
  *   head_corr[(a*3+c)*32 + o] over the taps (a, c) of the 3x3 kernel that fall outside the
  *   upsampled image (the deconv bias those zero-padded taps must not carry).
+ *   Compact form (no new field: recognised from the call): with a 3x3 / stride 1 / pad 1 geometry,
+ *   K == 4*in_c instead of 9*in_c means B = [q = 4][o = 32][j = 4][in_c] (ldb >= 4*in_c): parity q's
+ *   weights at its 2 x 2 taps (ty, tx) = (dy + j/2, dx + j%2) only -- the other five taps of a
+ *   composed head are zero by construction (the k2 s2 deconv under a 3x3 conv reaches two h0 rows
+ *   and two h0 columns per parity).  Same result as the dense form on the patch-conv engine, bit
+ *   for bit, in 4/9 of its K steps.  Runs on DP_TILE_CV3_256x256 / DP_TILE_CV3_384x128 only (the
+ *   auto choice: 384x128 when the side % 48 == 0, else 256x256); a shape those cannot take (side
+ *   % 16 != 0, relu_a, M * in_c >= 2^30) or any other hint is DP_ERR_ARG -- the dense weights are
+ *   a different buffer, so there is no fallback.  bias, head_w, head_b, head_corr ([9][32]) are
+ *   those of the dense form.
  */
 typedef struct dp_gemm_args {
   int32_t M, N, K;
@@ -222,7 +232,8 @@ enum { DP_TILE_AUTO = 0, DP_TILE_128x128 = 1, DP_TILE_256x64 = 2, DP_TILE_256x32
    2. the fused 1x1 head (head_w with DP_STORE_ROWS) always runs on DP_TILE_256x32 and
       DP_STORE_HEAD_PS on a 128-column conv engine (the hint is kept only if it is
       DP_TILE_BIG_256x128, DP_TILE_CV3_256x256 or DP_TILE_CV3_384x128): other hints are ignored,
-      not rejected;
+      not rejected -- except for the compact form (K == 4*in_c), which only the two DP_TILE_CV3_*
+      engines walk: any other hint is DP_ERR_ARG;
    3. hints 1 - 3 (DP_TILE_128x128, 256x64, 256x32: the 4-column engines) take everything else
       except head_corr (DP_ERR_ARG);
    4. every hint >= DP_TILE_BIG_256x256: the 8-column rules (DP_ERR_SHAPE, then DP_ERR_ALIGN);
@@ -262,7 +273,8 @@ enum { DP_TILE_AUTO = 0, DP_TILE_128x128 = 1, DP_TILE_256x64 = 2, DP_TILE_256x32
    DP_TILE_CV3_384x128 (ABI 14): the same engine on 24 x 16-pixel tiles of 128 output channels
    (side % 48 == 0, N == 128, with head_corr: the border-corrected composed conv, or
    DP_STORE_HEAD_PS): the auto choice for the former (out_conv∘head.0 at 768^2: 1536 tiles =
-   6 rounds); a hint for the composed depth head, whose auto choice stays the 512 x 128 engine.
+   6 rounds); a hint for the dense composed depth head, whose auto choice stays the 512 x 128
+   engine, and the auto choice for its compact form (K == 4*in_c, above).
    DP_TILE_SPLITK_256x256 (ABI 11, a hint only, needs a workspace): split-K for small grids -- the
    256 x 256 tiles' K steps split over up to (CUs / tiles) workgroups that write fp32 partials into
    the workspace, then a reduce launch sums them in split order and runs the epilogue

@@ -89,8 +89,13 @@ int gemm_plan(const dp_gemm_args* a, GemmP& p, int& tile) {
   if (a->c_dtype != DP_F32 && a->c_dtype != a->dtype) return DP_ERR_DTYPE;
   if (a->accumulate && a->c_dtype != DP_F32) return DP_ERR_DTYPE;
   if (a->pos && (a->pos_group <= 0)) return DP_ERR_ARG;
+  // the composed depth head's compact form: DP_STORE_HEAD_PS over a 3x3 / stride 1 / pad 1 conv
+  // geometry with K = 4 in_c -- B holds each parity's 2 x 2 non-zero taps only ([q][o][j][in_c],
+  // dp_mi355x.h); the patch-conv engine alone walks it
+  const bool hps4 = a->a_mode == DP_A_CONV && a->store_mode == DP_STORE_HEAD_PS && a->k_h == 3 && a->k_w == 3 &&
+                    a->stride == 1 && a->pad == 1 && a->K == 4 * a->in_c;
   if (a->a_mode == DP_A_CONV) {
-    if (a->in_c % BK != 0 || a->k_h * a->k_w * a->in_c != a->K) return DP_ERR_SHAPE;
+    if (a->in_c % BK != 0 || (a->k_h * a->k_w * a->in_c != a->K && !hps4)) return DP_ERR_SHAPE;
     if (a->out_h <= 0 || a->out_w <= 0 || a->stride <= 0 || a->M % (a->out_h * a->out_w) != 0)
       return DP_ERR_SHAPE;
   }
@@ -152,7 +157,13 @@ int gemm_plan(const dp_gemm_args* a, GemmP& p, int& tile) {
     // 32-column parity groups must not straddle a wave's columns (TN = 32 or 64); the patch-conv
     // engine (one parity per wave) only when asked for: at 768^2 it runs 347 - 355 us in-frame vs
     // 249 - 255 on the 512 x 128 engine (profiles/r03w/)
-    if (tile != DP_TILE_CV3_256x256 && tile != DP_TILE_CV3_384x128 && tile != DP_TILE_BIG_256x128)
+    // The compact form (hps4) exists on the patch-conv engine only, 24-row tiles where the side
+    // allows; a shape that engine cannot take is an error below (the dense weights are another
+    // buffer: no fallback).
+    if (hps4) {
+      if (tile == DP_TILE_AUTO) tile = a->out_w % 48 == 0 ? DP_TILE_CV3_384x128 : DP_TILE_CV3_256x256;
+      else if (tile != DP_TILE_CV3_256x256 && tile != DP_TILE_CV3_384x128) return DP_ERR_ARG;
+    } else if (tile != DP_TILE_CV3_256x256 && tile != DP_TILE_CV3_384x128 && tile != DP_TILE_BIG_256x128)
       tile = a->M >= 512 * 256 ? DP_TILE_BIG_512x128 : DP_TILE_BIG_256x128;
   } else if (a->head_w) {
     if (a->N > 32 || a->store_mode != DP_STORE_ROWS) return DP_ERR_SHAPE;
@@ -371,6 +382,7 @@ int gemm_plan(const dp_gemm_args* a, GemmP& p, int& tile) {
         (long long)a->M * a->in_c >= (1LL << 30) || (long long)a->N * a->ldb >= (1LL << 31))
       return DP_ERR_ARG;
     if (!hps && a->store_mode != DP_STORE_ROWS) return DP_ERR_ARG;
+    if (hps4 && a->relu_a) return DP_ERR_ARG;   // (the compact walk has no ReLU-prologue instantiation)
     if (bc && (a->c_dtype == DP_F32 || a->R1 || a->R2 || a->N % 128 != 0)) return DP_ERR_ARG;
     if (!hps && !bc && (a->c_dtype == DP_F32 || a->N % 256 != 0)) return DP_ERR_ARG;
     if (th == 12 && (hps || bc)) return DP_ERR_ARG;

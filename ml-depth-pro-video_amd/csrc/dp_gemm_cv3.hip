@@ -62,8 +62,16 @@ constexpr int CV_STAMPS = 16, CV_STAMP_WGS = 4096;   // [6..9] (ABL 256): K-loop
                                                        // the steps of taps 1..8; [10..13]: of the tap-0 steps;
                                                        // [14] / [15]: whole steps of taps 1..8 / tap 0
 __device__ unsigned long long g_cv3_stamp[CV_STAMP_WGS * CV_STAMPS];
-template <typename K_, bool RELU, int BN, int EPI, int ABL = 0, int TH = 16>
+// NT: taps walked per channel block.  9: every tap, B = the packed conv weights.  4 (CV_EPI_HPS
+// only): the composed depth head's compact form -- parity q = 2 dy + dx of its 128 outputs (one
+// per wave) has non-zero weights only at the 2 x 2 taps (dy + j / 2, dx + j % 2), j = 0..3, so each
+// wave walks its own parity's four taps of the shared patch and B is [q][o][j][in_c] (K = 4 in_c):
+// K step (cb, j) streams columns j in_c + 64 cb of all 128 rows.  Same tap and channel-block order
+// as the dense walk, which only adds the exact zeros of the other five taps: bit-identical.
+template <typename K_, bool RELU, int BN, int EPI, int ABL = 0, int TH = 16, int NT = 9>
 __global__ void __launch_bounds__(512, 1) gemm_cv3_kernel(const GemmP p) {
+  constexpr bool CPT = NT == 4;
+  static_assert(NT == 9 || (CPT && EPI == CV_EPI_HPS), "taps per channel block");
   using G = CvGeo<TH>;
   constexpr int FM = G::FM, HQ = G::HQ, PPW = G::PPW, CV_PATCH_B = G::PATCH_B, CV_PIX = G::PIX;
   constexpr bool TIGHT = G::TIGHT;
@@ -91,7 +99,7 @@ __global__ void __launch_bounds__(512, 1) gemm_cv3_kernel(const GemmP p) {
   const int img = sp / tpi, r_ = sp - img * tpi;
   const int y0 = (r_ / tpr) * TH, x0 = (r_ % tpr) * CV_TW, n0 = tn * BN;
   const int cin = p.in_c, CB = cin / 64;
-  const int KT = CB * 9;
+  const int KT = CB * NT;
 
   // patch pieces of this lane: byte offset of its 16-B chunk (channel block 0) in the input map, or
   // CV_PAD when the pixel is in the zero padding or past the patch (read as zeros: past the end of
@@ -123,10 +131,11 @@ __global__ void __launch_bounds__(512, 1) gemm_cv3_kernel(const GemmP p) {
   // byte offset of this lane's weight row (prow) from the piece's scalar base p.B + (h 128 + i 64)
   // ldb + 64 t (host: N * ldb < 2^31): one VGPR, the rest wave-uniform
   const uint32_t boff = 2u * (uint32_t)((n0 + prow) * (int)p.ldb + pchunk * 8);
+  auto kcol = [&](int t) { return CPT ? (t & 3) * cin + (t >> 2) * 64 : 64 * t; };   // B column of K step t
   auto issue_b = [&](int h, int t) {   // half h of weight step t -> stage t & 1
     const uint32_t dst = lds0 + WOFF + (t & 1) * B_B + h * HALF + wave_u * 1024;
     #pragma unroll
-    for (int i = 0; i < 2; ++i) glds16s(boff, p.B + (long long)(h * 128 + i * 64) * p.ldb + 64 * t, dst + i * 8192);
+    for (int i = 0; i < 2; ++i) glds16s(boff, p.B + (long long)(h * 128 + i * 64) * p.ldb + kcol(t), dst + i * 8192);
   };
   auto issue_patch1 = [&](int cb, int buf, int i) {   // piece i of the wave's PPW patch pieces
     int c0 = wave * PPW * 64 + lane;              // the lane's chunk of piece 0
@@ -165,7 +174,8 @@ __global__ void __launch_bounds__(512, 1) gemm_cv3_kernel(const GemmP p) {
   typedef __attribute__((address_space(3))) const u32x4_t lds_u4;   // (16-B alignment known: one ds_read_b128)
   uint32_t abase[8][2], bbase[2];
   {
-    const int PB = wm * FM * CV_PW + frow;
+    // (CPT: + the wave's parity offset (dy, dx), so that tap j is c = (.. + j / 2) 18 + j % 2)
+    const int PB = wm * FM * CV_PW + frow + (CPT ? (wn >> 1) * CV_PW + (wn & 1) : 0);
     #pragma unroll
     for (int v = 0; v < 8; ++v)
       #pragma unroll
@@ -271,11 +281,17 @@ __global__ void __launch_bounds__(512, 1) gemm_cv3_kernel(const GemmP p) {
     constexpr int ST0 = decltype(st0_tag)::value;
     constexpr int pb = ST0;                       // (cb & 1 = cb * 9 & 1)
     const bool nb = cb + 1 < CB;
+    // the next block's patch pieces go out in the block's first NS steps, [tap PPW / NS, (tap + 1)
+    // PPW / NS) in step tap: one per step on the 9-tap walk (NS = PPW), 2 or 3 on the 4-tap one
+    // (NS = 3: the last piece must be out one step before the block's last, whose wait retires it)
+    constexpr int NS = PPW < NT - 1 ? PPW : NT - 1;
     #pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-      const int ky = tap / 3, kx = tap - ky * 3, st = (ST0 + tap) & 1;
-      const int t = cb * 9 + tap;
-      const bool np = tap < PPW && nb;            // this step streams piece `tap` of the next block's patch
+    for (int tap = 0; tap < NT; ++tap) {
+      const int ky = CPT ? tap >> 1 : tap / 3, kx = CPT ? tap & 1 : tap - ky * 3;
+      const int st = CPT ? tap & 1 : (ST0 + tap) & 1;   // (NT = 4: step t = 4 cb + tap, t & 1 = tap & 1)
+      const int t = cb * NT + tap;
+      const bool np = tap < NS && nb;             // this step streams pieces of the next block's patch
+      const int pi0 = tap * PPW / NS, pn = (tap + 1) * PPW / NS - pi0;
       const bool n2 = t + 2 < KT;
       if constexpr ((ABL & 256) != 0) so_ = tap == 0 ? 4 : 0;
       const unsigned long long s0_ = tick();
@@ -292,7 +308,8 @@ __global__ void __launch_bounds__(512, 1) gemm_cv3_kernel(const GemmP p) {
       // vmcnt accounting (per wave, retired in issue order; W = 2 pieces = a weight half, P = a
       // patch piece; NBH = 2, at NBH = 1 there is no second half):
       //   step t        issued, oldest first, at the wait            wait   left in flight
-      //   tap < PPW     [W W](t+1)  P(tap)  W(t+2, half 0)           3      P, W(t+2, half 0)
+      //   tap < NS      [W W](t+1)  P(tap)  W(t+2, half 0)           3      P, W(t+2, half 0)
+      //     (NT = 4: pn = 2 or 3 pieces P in a step: the wait is pn + 2)
       //   other taps    [W W](t+1)  W(t+2, half 0)                   2      W(t+2, half 0)
       //   t + 2 >= KT   [W W](t+1)  (no patch: the last block)       0
       // (tap < PPW with t + 2 >= KT cannot happen: a next block means 9 more steps; the 1 is kept
@@ -301,14 +318,19 @@ __global__ void __launch_bounds__(512, 1) gemm_cv3_kernel(const GemmP p) {
       // two barriers before the next block's first fragment read (the stagger of the wave rows
       // needs one barrier more than the wait's own).
       readA(0, ky, kx, pb); readB(0, st); readB(1, st);
-      if (np && !(ABL & 2) && !(ABL & 128)) issue_patch1(cb + 1, pb ^ 1, tap);
+      if (np && !(ABL & 2) && !(ABL & 128)) {
+        #pragma unroll
+        for (int i = 0; i < pn; ++i) issue_patch1(cb + 1, pb ^ 1, pi0 + i);
+      }
       relu_early();
       bar(); mma(0, 0); mma(0, 1); bar();
       readA(1, ky, kx, pb);
       if (n2 && !(ABL & 2) && !(ABL & 64)) issue_b(0, t + 2);
       relu_early();
       const unsigned long long v0_ = tick();
-      if (np) { if (n2) wait_vmcnt<1 + 2>(); else wait_vmcnt<1>(); }
+      if (np && pn == 3) { if (n2) wait_vmcnt<3 + 2>(); else wait_vmcnt<3>(); }
+      else if (np && pn == 2) { if (n2) wait_vmcnt<2 + 2>(); else wait_vmcnt<2>(); }
+      else if (np) { if (n2) wait_vmcnt<1 + 2>(); else wait_vmcnt<1>(); }
       else { if (n2) wait_vmcnt<2>(); else wait_vmcnt<0>(); }
       if constexpr ((ABL & 256) != 0) st_[6 + so_] += tick() - v0_;
       if (NBH == 2 && n2 && !(ABL & 2) && !(ABL & 64)) issue_b(1, t + 2);
@@ -366,7 +388,10 @@ __global__ void __launch_bounds__(512, 1) gemm_cv3_kernel(const GemmP p) {
       #pragma unroll
       for (int r = 0; r < 4; ++r) hw[fn][r] = p.head_w[(nw & 31) + fn * 16 + 4 * g + r];
     const long long W2 = 2LL * S;
-    #pragma unroll 1
+    // unrolled: with a rolled loop acc[fm] is indexed by a register, which put the whole accumulator
+    // array in scratch memory -- through the K loop too (a scratch load and store per two MFMAs:
+    // 867 us dense on 24-row tiles at 768^2, profiles/head_ps_compact/)
+    #pragma unroll
     for (int fm = 0; fm < FM; ++fm) {
       const int y = y0 + wm * FM + fm, x = x0 + t;
       float z[FN][4];
@@ -485,6 +510,10 @@ template <typename K_>
 int launch_cv3(const GemmP& p0, hipStream_t s, int th) {
   GemmP p = p0;
   const int S = p.out_w;
+  // the composed head's compact form (4 taps per parity): recognised by its K
+  const bool cpt = p.store_mode == DP_STORE_HEAD_PS && p.K == 4 * p.in_c;
+  if (!cpt && p.K != 9 * p.in_c) return DP_ERR_ARG;
+  if (cpt && (p.relu_a || th == 12)) return DP_ERR_ARG;
   if (p.k_h != 3 || p.k_w != 3 || p.stride != 1 || p.pad != 1 || p.in_h != S || p.in_w != S || p.out_h != S ||
       S % CV_TW || S % th || p.in_c % 64 || p.M % (S * S) || p.row_group || (p.head_w && p.store_mode != DP_STORE_HEAD_PS) ||
       p.gamma || p.pos || p.accumulate || (p.act != DP_ACT_NONE && p.act != DP_ACT_RELU))
@@ -513,6 +542,12 @@ int launch_cv3(const GemmP& p0, hipStream_t s, int th) {
   // the planner's own debug bits (16, 32, 64, 1024, ...) never select one; an ablation
   // value without a variant runs the normal kernel
   const int abl = (p.dbg & (1 << 24)) ? p.dbg & 2047 : 0;
+  if (cpt) {
+    if (th == 24) hipLaunchKernelGGL((gemm_cv3_kernel<K_, false, 128, CV_EPI_HPS, 0, 24, 4>), grid, dim3(512), 0, s, p);
+    else hipLaunchKernelGGL((gemm_cv3_kernel<K_, false, 128, CV_EPI_HPS, 0, 16, 4>), grid, dim3(512), 0, s, p);
+    DP_CHECK_LAUNCH();
+    return 0;
+  }
   if (th == 24) {   // 24 x 16-pixel tiles, 128 channels: 2 x 64 KiB patches + 2 x 16 KiB weight steps
     if (epi == CV_EPI_BC && !p.relu_a && abl == 8) hipLaunchKernelGGL((gemm_cv3_kernel<K_, false, 128, CV_EPI_BC, 8, 24>), grid, dim3(512), 0, s, p);
     else if (epi == CV_EPI_BC && !p.relu_a && abl == 264) hipLaunchKernelGGL((gemm_cv3_kernel<K_, false, 128, CV_EPI_BC, 264, 24>), grid, dim3(512), 0, s, p);

@@ -91,8 +91,27 @@ def compose_head(wd: torch.Tensor, bd: torch.Tensor, w2: torch.Tensor, b2: torch
     corr = torch.einsum("ocab,c->abo", w2, bd).contiguous()             # [3, 3, o]
     bias = (b2 + corr.sum(dim=(0, 1))).repeat(4).contiguous()           # interior: all 9 taps
     w_conv = wc.reshape(4 * o_n, 3, 3, ci_n).permute(0, 3, 1, 2)            # as a Conv2d weight [(q,o), ci, ty, tx]
-    return {"head.ps.w": ops.conv_weight(w_conv, dt), "head.ps.b": bias,
+    return {"head.ps.w": ops.conv_weight(w_conv, dt), "head.ps.w4": compact_head_w(wc, dt), "head.ps.b": bias,
             "head.ps.corr": corr.reshape(-1).contiguous()}
+
+
+def compact_head_w(wc: torch.Tensor, dt) -> torch.Tensor:
+    """The composed head conv W'[q, o, ty, tx, ci] (fp32, compose_head) without its zero taps:
+    B[(q, o)][(j, ci)] with j the parity's 2 x 2 taps (ty, tx) = (dy + j // 2, dx + j % 2) in
+    ascending order (dp_gemm's compact DP_STORE_HEAD_PS form, K = 4 ci).  Parity row offset dy only
+    reaches h0 rows y + dy - 1 and y + dy (a k2 s2 deconv under a 3x3 conv), the same for dx, so
+    the other five taps are the zeros `wc` was allocated with; checked here, since a W' built any
+    other way would silently lose them."""
+    q_n, o_n, _, _, ci_n = wc.shape
+    out = torch.empty(q_n, o_n, 4, ci_n, dtype=torch.float32, device=wc.device)
+    for q in range(q_n):
+        dy, dx = q >> 1, q & 1
+        keep = torch.zeros(3, 3, dtype=torch.bool, device=wc.device)
+        keep[dy:dy + 2, dx:dx + 2] = True
+        if wc[q][:, ~keep].ne(0).any():
+            raise AssertionError(f"composed head conv: parity {q} has a non-zero weight outside its 2 x 2 taps")
+        out[q] = wc[q][:, dy:dy + 2, dx:dx + 2].reshape(o_n, 4, ci_n)
+    return out.reshape(q_n * o_n, 4 * ci_n).to(dt).contiguous()
 
 
 def compose_head0(w0: torch.Tensor, b0: torch.Tensor, wo: torch.Tensor, bo: torch.Tensor, dt) -> Dict[str, object]:
@@ -456,6 +475,10 @@ class Engine:
         # decoder out_conv composed into the head's first conv (compose_head0); DP_HEAD0_COMPOSE=0:
         # separate (the per-stage parity test reads fusion 0's output on that path)
         self.head0_compose = os.environ.get("DP_HEAD0_COMPOSE", "1") == "1" and "head.0c.w" in packed
+        # the composed head conv walked compact (each parity's 2 x 2 non-zero taps, K = 4 * 128, on the
+        # patch-conv engine) instead of dense on the 512 x 128 engine; DP_HEAD_PS_COMPACT=0: dense
+        # (also what a packed set from before the compact weights runs)
+        self.head_ps_compact = os.environ.get("DP_HEAD_PS_COMPACT", "1") == "1" and "head.ps.w4" in packed
         # softmax scale * log2(e) folded into the qkv epilogue (per-column gamma on Q) so that attention
         # takes one exp2 per score (dp_attention_log2q)
         self.qkv_gamma = ops.log2q_gamma(HEADS, D // HEADS, dev)
@@ -809,7 +832,9 @@ class Engine:
                         border_corr=P["head.0c.corr"])
         else:
             self._conv3(feats, 768, 256, P["head.0.w"], self.h0, 128, bias=P["head.0.b"])
-        ops.gemm(self.h0, P["head.ps.w"], self.canonical, M=768 * 768, N=128, K=9 * 128,
+        taps = 4 if self.head_ps_compact else 9
+        ops.gemm(self.h0, P["head.ps.w4" if self.head_ps_compact else "head.ps.w"], self.canonical,
+                 M=768 * 768, N=128, K=taps * 128,
                  conv=dict(in_h=768, in_w=768, in_c=128, k=3, stride=1, pad=1, out_h=768, out_w=768),
                  bias=P["head.ps.b"], head_w=P["head.4.w"], head_b=P["head.4.b"], head_corr=P["head.ps.corr"])
         return self.canonical, self.fov_deg

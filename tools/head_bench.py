@@ -52,6 +52,23 @@ def main():
                        ("head.ps (composed deconv + conv + 1x1)", f1, 2.0 * S * S * 128 * 1152)):
         us = timeit(f)
         print(f"{lab:40s} {us:7.1f} us  {fl / us / 1e6:6.1f} TF", flush=True)
+    if "--compact" in sys.argv:
+        # head.ps alone, alternating: dense on the 512 x 128 engine (the dense auto choice), dense on
+        # the patch-conv engine (24-row tiles), and the compact form (each parity's 2 x 2 taps, K = 4 *
+        # 128) on the patch-conv engine's 24- and 16-row tiles; `--compact N` samples each (default 3)
+        from depth_pro._lib import DP_TILE_BIG_512x128, DP_TILE_CV3_256x256, DP_TILE_CV3_384x128
+        i = sys.argv.index("--compact")
+        n = int(sys.argv[i + 1]) if i + 1 < len(sys.argv) and sys.argv[i + 1].isdigit() else 3
+        wps4 = (torch.randn(128, 4 * 128, device=dev, generator=g) * 0.03).to(dt)
+        ps = lambda w, taps, tile: (lambda: ops.gemm(h0, w, out, M=S * S, N=128, K=taps * 128, conv=conv(128),  # noqa: E731
+                                                     bias=bps, head_w=hw, head_b=0.1, head_corr=corr, tile=tile))
+        variants = (("dense 512x128", ps(wps, 9, DP_TILE_BIG_512x128)),
+                    ("dense patch-conv 24-row", ps(wps, 9, DP_TILE_CV3_384x128)),
+                    ("compact patch-conv 24-row", ps(wps4, 4, DP_TILE_CV3_384x128)),
+                    ("compact patch-conv 16-row", ps(wps4, 4, DP_TILE_CV3_256x256)))
+        for k in range(n):
+            for lab, f in variants:
+                print(f"head.ps sample {k}: {lab:28s} {timeit(f, 1.0):7.1f} us", flush=True)
     if "--ablate" in sys.argv:
         # the big engine's timing ablations (dp_gemm_debug_flags; results are wrong): what bounds head.ps
         from depth_pro import _lib

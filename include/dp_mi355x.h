@@ -1089,8 +1089,9 @@ int dp_estimate_normals(const double* points, const int32_t* n_dev, int32_t n_ma
  *   Bounds: no kernel waits on another workgroup; a find walks at most the chain to its root, which
  *   halving keeps short but which is not bounded below the region's size.
  *   Stated difference: the reference measures a region by cv2.contourArea of its traced outline and
- *   drops those of 5 or less; here the area is the cell count.  findContours, approxPolyDP, the polygons
- *   file are not built (detect_and_split_l_shapes belongs to the shapes stage: "L-shape split" below).
+ *   drops those of 5 or less; here the area is the cell count.  findContours, approxPolyDP and the polygons
+ *   file are the next section, "Floor-plan polygons", which does measure a region by its traced outline
+ *   (detect_and_split_l_shapes belongs to the shapes stage: "L-shape split" below).
  *
  * Picture (dp_floorplan_image): image_out uint8 [max_cells][3], RGB, H x W as the grids (row 0 = smallest z).
  *  12. White background.  A cell whose label has a table row with area >= min_area is filled; the cells
@@ -1123,6 +1124,136 @@ int dp_grid_regions(const uint8_t* grid, const uint32_t* density, const float* h
 int dp_floorplan_image(const int32_t* labels, const int32_t* dims, int32_t max_cells, const double* table,
                        const int32_t* n_regions_dev, int32_t max_regions, double resolution, double min_area,
                        double max_height, int32_t color_by_height, uint8_t* image_out, dp_stream_t stream);
+
+/*
+ * ---- Floor-plan polygons (additive to ABI 20, csrc/dp_outline.hip) ----------------------------------
+ * The rest of the reference's cleaned_pointcloud_to_floorplan.py behind the regions: the outline of each
+ * region (cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE), process_height_slice :309), its
+ * simplification (approximate_contour :314-387: contourArea, arcLength, approxPolyDP, Polygon.is_valid, the
+ * rectangle snap) and the mean height that labels the polygons file (create_height_slices :143).  The
+ * floor-plan section's conventions hold: dims and n_regions are read ON THE DEVICE, buffers have the
+ * caller's capacity, everything runs on the caller's stream with no synchronisation and no host read-back,
+ * argument errors are returned as DP_ERR_* before any launch, no kernel waits on another workgroup, and
+ * every loop is bounded by a count known at its start.  The block is additive: no existing entry point or
+ * layout changes, and DP_ABI_VERSION stays 20.  Vertices are (x, y) = (gx, gz) in grid units.
+ * OpenCV, skimage and shapely are not available to check against; the rules below are the specification
+ * (restated sequentially in tests/outline_numpy.py, pinned to scipy where scipy can pin them).
+ *   workspace  >= dp_outline_workspace_size(max_cells, max_regions, max_vertices) bytes of device memory,
+ *              8-byte aligned, owned by the call until the stream has passed it (content need not be
+ *              initialised): about 20 bytes per vertex and 100 per region, nothing per cell.  Both calls
+ *              take the same size; dp_simplify_outlines must get the max_regions and max_vertices of the
+ *              outlines it reads.
+ *
+ * Outline (dp_region_outlines), for each region with a table row, r < R = min(*n_regions, max_regions),
+ * label r + 1, read from `labels` as dp_grid_regions wrote them:
+ *   O1. Start.  s = the region's first cell in row-major order (the cell that gives it its label).
+ *   O2. Border following (Suzuki-Abe's outer border as OpenCV runs it).  Directions are numbered
+ *       counter-clockwise on the screen with z down: 0 E, 1 NE, 2 N, 3 NW, 4 W, 5 SW, 6 S, 7 SE.  From s
+ *       look clockwise beginning at W (W, NW, N, NE, E, SE, S, SW) for the first cell of the region, i1.
+ *       None: the outline is the single vertex s.  Otherwise i2 = i1, i3 = s, and repeat: look
+ *       counter-clockwise around i3, beginning one step after the direction of i2, for the first cell i4
+ *       of the region (i2 itself is the eighth candidate); emit i3; stop if i4 == s and i3 == i1;
+ *       otherwise i2 = i3, i3 = i4.  A cell on a one-cell-wide part is emitted once per pass.  Cells outside
+ *       the grid are no cells of the region.  Holes are never entered: the walk keeps the outside on its
+ *       searching side.
+ *   O3. CHAIN_APPROX_SIMPLE.  An emitted cell is a vertex iff the step leaving it differs from the step
+ *       that arrived at it, taken cyclically (the start's arriving step is the last step of the walk).  The
+ *       start is always a vertex: it arrives by W, NE, N or NW and leaves by E, SE, S or SW.
+ *   O4. columns_out int64 [max_regions][DP_OUTLINE_INT_COLUMNS], row r: 0 vertices; 1 emitted (border)
+ *       cells; 2 the signed shoelace sum  sum_i (x_i * y_i+1 - x_i+1 * y_i)  over the vertices, last to
+ *       first included, exact; 3 the start cell gz * W + gx (-1: the label has no cell, all columns 0).
+ *       measures_out fp64 [max_regions][DP_OUTLINE_REAL_COLUMNS], row r: 0 area = |sum| / 2
+ *       (cv2.contourArea); 1 perimeter (cv2.arcLength, closed): over consecutive vertices, last to first
+ *       included, the float32 square root of dx * dx + dy * dy -- dx, dy converted to float32, both products
+ *       and their sum rounded to float32 -- summed in fp64 in vertex order (the sum is exact below 2^29,
+ *       so the order cannot show).
+ *   O5. offsets_out int32 [max_regions + 1], vertices_out int32 [max_vertices][2].  Region r's vertices are
+ *       written, in the order of O2 from s, at offsets[r] .. offsets[r + 1] iff the vertex counts of
+ *       regions 0 .. r together are <= max_vertices; otherwise it keeps its columns, writes no vertices
+ *       (offsets[r + 1] = offsets[r]) and raises the overflow flag.  So the first region that does not fit
+ *       and every later one are left out, and nothing is written at or past max_vertices.  A region past
+ *       max_regions is skipped.
+ *       stats_out fp64 [8]: regions, rows R, vertices of all rows, vertices written, vertex overflow flag,
+ *       region overflow flag (regions > max_regions), H, W.
+ *   Method: a workgroup (one wave) per region walks its cycle.  The successor in O2 is a function of (cell,
+ *   direction of the previous cell), so the border states form disjoint cycles and the walk is bounded by
+ *   8 * (cells of the region), counted beforehand.  Lane k looks at the k-th candidate of a search and a
+ *   ballot takes the first, so a step is one round of loads.  The walk runs twice: once for the columns,
+ *   and, after one workgroup has scanned the counts into offsets, once more to write.
+ *
+ * Simplification (dp_simplify_outlines), for each row r in turn; the reference runs in height-threshold
+ * mode, so its own halvings apply.  polygons_out fp64 [max_regions][DP_POLYGON_COLUMNS] has one row per
+ * region whether it keeps a polygon or not.
+ *   S1. Area filter.  area * (resolution * resolution) < min_area / 4: no polygon (drop reason 1).  The
+ *       reference divides min_area by 4 twice; the caller's min_area is after the first division.
+ *   S2. epsilon = 0.005 * perimeter (alpha 0.01 halved).
+ *   S3. Closed Douglas-Peucker on the integer vertices (cv2.approxPolyDP, closed).  Anchors: start at vertex
+ *       0; three times, move to the vertex farthest from the current one (largest squared distance, first
+ *       of equals in ring order starting after the current one).  The last two vertices visited are the
+ *       anchors A (visited second) and B (visited last).  Early exit: if the last largest squared distance
+ *       is <= epsilon * epsilon the result is the single vertex A, and S4 drops it.  Otherwise the ring is
+ *       split into the chains A..B and B..A.  A chain keeps its interior vertex with the largest |cross| to
+ *       the chord if cross^2 > epsilon^2 * |chord|^2 -- the cross product an exact integer, (double)cross *
+ *       (double)cross against (epsilon * epsilon) * (double)(dx * dx + dy * dy) in fp64, the first of equal
+ *       maxima in ring order -- and is split there, recursively.  The result is the kept vertices in ring
+ *       order beginning at A, which is where OpenCV's output begins.
+ *       Stated difference: approxPolyDP ends with a clean-up pass over nearly collinear neighbours.  It is
+ *       NOT built: its exact form could not be stated with certainty, and neither it nor the rest of S3 can
+ *       be checked against OpenCV where this library is built and tested.
+ *   S4. Fewer than 3 vertices: no polygon (drop reason 2).
+ *   S5. Polygon.is_valid and area > 0, exact in integers.  No polygon (drop reason 3) if two vertices of the
+ *       ring coincide, two non-adjacent edges share a point (touching included), two adjacent edges overlap
+ *       (a spike: collinear and folding back), or the ring's shoelace sum is 0.
+ *   S6. Rectangle snap.  With 4 to 6 vertices: the ring's convex hull and the hull's minimum-area rectangle
+ *       by rules 2 and 3 of "Cluster shapes" (hull, calipers, ties to the smallest edge, angle folded into
+ *       [0, 90)), in fp64.  ring_area = |shoelace sum| / 2, rect_area = width * height.  If |rect_area -
+ *       ring_area| / ring_area < 0.2 the polygon is the four corners cv2.boxPoints gives for (centre,
+ *       (width, height), angle): with b = cos(angle) / 2, a = sin(angle) / 2:
+ *         p0 = (cx - a h - b w, cy + b h - a w), p1 = (cx + a h - b w, cy - b h - a w), p2 = 2 c - p0,
+ *         p3 = 2 c - p1, flag 1 (snapped).  Otherwise the polygon is the ring.
+ *       Stated difference: the reference runs cv2.minAreaRect on float32 points with its own angle
+ *       convention and measures the float32 box; sin and cos here are the device's.
+ *   S7. polygons_out row r: 0 label r + 1; 1 vertices of the polygon (0 without one); 2 flags (1 =
+ *       snapped); 3 area in cells (the ring's, or the rectangle's when snapped; 0 without a polygon);
+ *       4 that area * (resolution * resolution); 5 epsilon; 6 drop reason: 0 kept, 1 too small, 2 fewer than
+ *       3 vertices, 3 invalid, 4 overflow (the outline's vertices were not written, or the polygon's do not
+ *       fit); 7 vertices of the outline.  polygon_offsets_out int32 [max_regions + 1],
+ *       polygon_vertices_out fp64 [max_polygon_vertices][2]: as O5, a polygon is written iff the polygons
+ *       of rows 0 .. r together fit max_polygon_vertices.
+ *       stats_out fp64 [8]: rows, polygons kept, their vertices, vertices written, rows dropped for
+ *       overflow, too small, fewer than 3, invalid.
+ *   Method: one workgroup per region.  S3 runs level by level: every undecided vertex carries the two ends
+ *   of its chain, a chain takes its arg-max with one 64-bit atomicMax of (|cross| << 32 | ~position) at its
+ *   start, the vertices on either side of a kept one take it as their new end, and rounds repeat until
+ *   none splits (at most as many as vertices).  A scan of the keep flags (dp_points.h) lists the ring.
+ *   S5 is all pairs of edges.  S6 is the LDS sort, chain and calipers that dp_cluster_shapes runs.
+ *   resolution not finite or <= 0, min_area not finite or < 0, a negative capacity: DP_ERR_SHAPE.
+ *
+ * Mean height (dp_floor_mean_height): mean_out fp64 [2] on the device = (the mean y of the raster's
+ * participants, rule 1 of "Occupancy floor plan"; their number).  No participants: height_threshold, as the
+ * reference.  One fp64 sum in an unspecified order, one division.
+ *
+ * The polygons file (Python: export_floorplan_text) holds the reference's world coordinates:
+ * shapely.affinity.scale with its default origin scales about the centre of the polygon's bounding box and
+ * the translation adds the grid origin, X = cx + (x - cx) * resolution + min_x with cx the bounding-box
+ * centre IN GRID UNITS, and likewise Z.  That is the reference's behaviour and is reproduced as it is; the
+ * plain origin + x * resolution coordinates are in the JSON beside it.
+ */
+#define DP_OUTLINE_INT_COLUMNS 4
+#define DP_OUTLINE_REAL_COLUMNS 2
+#define DP_POLYGON_COLUMNS 8
+int64_t dp_outline_workspace_size(int64_t max_cells, int64_t max_regions, int64_t max_vertices);
+int dp_region_outlines(const int32_t* labels, const int32_t* dims, int32_t max_cells, const int32_t* n_regions_dev,
+                       int32_t max_regions, int32_t max_vertices, int32_t* offsets_out, int32_t* vertices_out,
+                       int64_t* columns_out, double* measures_out, double* stats_out, void* workspace,
+                       int64_t workspace_bytes, dp_stream_t stream);
+int dp_simplify_outlines(const int32_t* offsets, const int32_t* vertices, const int64_t* columns, const double* measures,
+                         const int32_t* n_regions_dev, int32_t max_regions, int32_t max_vertices, double resolution,
+                         double min_area, int32_t max_polygon_vertices, int32_t* polygon_offsets_out,
+                         double* polygon_vertices_out, double* polygons_out, double* stats_out, void* workspace,
+                         int64_t workspace_bytes, dp_stream_t stream);
+int dp_floor_mean_height(const double* points, const int32_t* n_dev, int32_t n_max, double height_threshold,
+                         double* mean_out, dp_stream_t stream);
 
 /*
  * ---- L-shape split (additive to ABI 20, csrc/dp_lshape.hip) -----------------------------------------

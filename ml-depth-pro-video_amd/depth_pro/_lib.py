@@ -33,6 +33,7 @@ DP_FLOOR_MAX_DIM, DP_FLOOR_MAX_KERNEL, DP_FLOOR_COLUMNS = 8192, 15, 13
 DP_BOUNDARY_MAX_DIM, DP_BOUNDARY_MAX_T, DP_BOUNDARY_DIRS, DP_BOUNDARY_COUNTS = 16384, 32, 4, 3
 DP_BOUNDARY_DEPTH, DP_BOUNDARY_MASK, DP_BOUNDARY_INVERSE, DP_BOUNDARY_SEGMENT = 0, 1, 2, 64
 DP_LSHAPE_MAX_SIDE = 1024
+DP_OUTLINE_INT_COLUMNS, DP_OUTLINE_REAL_COLUMNS, DP_POLYGON_COLUMNS = 4, 2, 8
 DP_ABI_VERSION = 20
 
 _ERRORS = {1000: "DP_ERR_ARG", 1001: "DP_ERR_SHAPE", 1002: "DP_ERR_ALIGN", 1003: "DP_ERR_DTYPE"}
@@ -58,6 +59,7 @@ EXPORTS = (
     "dp_shape_rectangles", "dp_lshape_workspace_size", "dp_lshape_split",
     "dp_boundary_workspace_size", "dp_boundary_counts", "dp_boundary_edges",
     "dp_mesh_workspace_size", "dp_knn_exact", "dp_mesh_mean_distance", "dp_mesh_fan", "dp_mesh_clean_triangles",
+    "dp_outline_workspace_size", "dp_region_outlines", "dp_simplify_outlines", "dp_floor_mean_height",
 )
 
 
@@ -178,6 +180,10 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "dp_mesh_mean_distance": [vp, vp, vp, i32, i32, vp, vp, i64, vp],
         "dp_mesh_fan": [vp, vp, vp, i32, i32, vp, vp],
         "dp_mesh_clean_triangles": [vp, vp, i32, i32, vp, vp, vp, vp, i64, vp],
+        "dp_outline_workspace_size": [i64, i64, i64],
+        "dp_region_outlines": [vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp],
+        "dp_simplify_outlines": [vp, vp, vp, vp, vp, i32, i32, f64, f64, i32, vp, vp, vp, vp, vp, i64, vp],
+        "dp_floor_mean_height": [vp, vp, i32, f64, vp, vp],
     }
     for name, argtypes in sig.items():
         fn = getattr(lib, name)
@@ -193,6 +199,7 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.dp_lshape_workspace_size.restype = ctypes.c_int64
     lib.dp_boundary_workspace_size.restype = ctypes.c_int64
     lib.dp_mesh_workspace_size.restype = ctypes.c_int64
+    lib.dp_outline_workspace_size.restype = ctypes.c_int64
     lib.dp_gemm_debug_flags.argtypes = [ctypes.c_int]
     lib.dp_gemm_debug_flags.restype = ctypes.c_int
     ver = lib.dp_abi_version()

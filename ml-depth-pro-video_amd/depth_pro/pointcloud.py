@@ -39,6 +39,11 @@ Occupancy floor plan (the reference's `cleaned_pointcloud_to_floorplan.py` up to
 `occupancy_grid`, `grid_morphology`, `grid_regions`, `floorplan_image` and `floor_plan` (all four with the
 reference's height-threshold values) -- csrc/dp_floorplan.hip, no OpenCV, no host read-back;
 `floor_plan_summary` makes the one read-back.
+
+Floor-plan polygons (the rest of that file: `findContours`, `approximate_contour`, `save_floorplan_data`):
+`region_outlines`, `simplify_outlines`, `floor_mean_height` and `floor_polygons` on a `floor_plan` result --
+csrc/dp_outline.hip, no OpenCV, no shapely, no host read-back; `floor_polygons_summary` makes the one read-back
+and `export_floorplan_text` writes the reference's `{base}_floorplan.txt`.
 """
 
 from __future__ import annotations
@@ -1416,7 +1421,7 @@ def floor_plan(points: torch.Tensor, colors: Optional[torch.Tensor] = None, coun
     2.5).  Returns `occupancy_grid`'s dict with `cleaned` (the grid after morphology), `labels`, `n_regions`, `table`,
     `region_stats` and `image` added, and the parameters under `parameters`; all tensors on the device, nothing
     synchronised.  Stated differences: a region's area is its cell count (the reference: `contourArea` of a traced
-    outline); no contour simplification, no polygons, no text."""
+    outline); no text.  The traced outlines, their simplification and the polygons file are `floor_polygons`."""
     _check_floor(resolution, padding, float("nan") if height_threshold is None else float(height_threshold), max_cells,
                  close_size, close_iters, open_size, min_area, max_height, max_regions)
     out = occupancy_grid(points, colors, count, height_threshold, resolution, padding, max_cells)
@@ -1450,6 +1455,190 @@ def floor_plan_summary(plan: dict) -> dict:
     return {"origin": [float(small[2]), float(small[3])], "resolution": params["resolution"], "height": h, "width": w,
             "parameters": dict(params), "stats": {k: float(v) for k, v in zip(GRID_STATS, small[4:12])},
             "region_stats": {k: float(v) for k, v in zip(REGION_STATS, small[12:20])}, "regions": regions, "image": img}
+
+
+# ---- floor-plan polygons: outlines, simplification, the polygons file (csrc/dp_outline.hip) -----------
+
+OUTLINE_COLUMNS = ("vertices", "border_cells", "shoelace", "start_cell")
+OUTLINE_MEASURES = ("area", "perimeter")
+OUTLINE_STATS = ("regions", "rows", "vertices", "vertices_written", "vertex_overflow", "region_overflow", "height", "width")
+POLYGON_COLUMNS = ("label", "vertices", "flags", "area_cells", "area", "epsilon", "drop_reason", "outline_vertices")
+POLYGON_STATS = ("rows", "polygons", "vertices", "vertices_written", "overflow", "too_small", "too_few", "invalid")
+DROP_REASONS = ("kept", "too_small", "fewer_than_3_vertices", "invalid", "overflow")
+POLYGON_SNAPPED = 1
+
+_OUTLINE = "the floor-plan polygons run on the ROCm device (csrc/dp_outline.hip)"
+
+
+def _plan_args(plan: dict, keys):
+    """The device tensors `keys` of a `floor_plan` result, checked; (lib, device, max_regions, stream)."""
+    if not isinstance(plan, dict) or any(k not in plan for k in keys):
+        raise ValueError(f"plan must be a floor_plan result holding {', '.join(keys)}")
+    dev = plan[keys[0]].device
+    if dev.type != "cuda":
+        raise _lib.DPError(_OUTLINE)
+    for k in keys:
+        t = plan[k]
+        if not torch.is_tensor(t) or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"plan[{k!r}] must be a contiguous tensor on the plan's device")
+    return _lib.load(), dev, int(plan["table"].shape[0]), torch.cuda.current_stream(dev).cuda_stream
+
+
+def _check_capacity(name: str, v) -> int:
+    if not 0 <= int(v) < 2 ** 31:
+        raise ValueError(f"{name} must be in [0, 2^31 - 1] (got {v})")
+    return int(v)
+
+
+def region_outlines(plan: dict, max_vertices: int = 1 << 20) -> dict:
+    """The outline of every region of a `floor_plan` result (`dp_region_outlines`): `cv2.findContours(RETR_EXTERNAL,
+    CHAIN_APPROX_SIMPLE)` restated as rules O1-O5 of the header.  Adds to `plan` and returns it: `outline_offsets`
+    (max_regions + 1,) int32, `outline_vertices` (max_vertices, 2) int32 (x = gx, y = gz), `outline_columns`
+    (max_regions, 4) int64 in `OUTLINE_COLUMNS` order, `outline_measures` (max_regions, 2) float64 (`contourArea`,
+    `arcLength`), `outline_stats` (8,) float64 in `OUTLINE_STATS` order.  A region whose vertices do not fit keeps its
+    columns, writes none and raises stats["vertex_overflow"].  Asynchronous, no read-back."""
+    mv = _check_capacity("max_vertices", max_vertices)
+    lib, dev, mr, stream = _plan_args(plan, ("labels", "dims", "n_regions", "table"))
+    lab, dims, nreg = plan["labels"], plan["dims"], plan["n_regions"]
+    if lab.dtype != torch.int32 or dims.dtype != torch.int32 or dims.numel() != 2 or nreg.dtype != torch.int32 or nreg.numel() != 1:
+        raise ValueError("plan labels, dims and n_regions must be int32 tensors as floor_plan returns them")
+    mc = lab.numel()
+    ws = torch.empty(int(lib.dp_outline_workspace_size(mc, mr, mv)), dtype=torch.uint8, device=dev)
+    plan["outline_offsets"] = torch.zeros(mr + 1, dtype=torch.int32, device=dev)
+    plan["outline_vertices"] = torch.empty(mv, 2, dtype=torch.int32, device=dev)
+    plan["outline_columns"] = torch.zeros(mr, len(OUTLINE_COLUMNS), dtype=torch.int64, device=dev)
+    plan["outline_measures"] = torch.zeros(mr, len(OUTLINE_MEASURES), dtype=torch.float64, device=dev)
+    plan["outline_stats"] = torch.empty(8, dtype=torch.float64, device=dev)
+    check(lib.dp_region_outlines(lab.data_ptr(), dims.data_ptr(), mc, nreg.data_ptr(), mr, mv, plan["outline_offsets"].data_ptr(),
+                                 plan["outline_vertices"].data_ptr(), plan["outline_columns"].data_ptr(),
+                                 plan["outline_measures"].data_ptr(), plan["outline_stats"].data_ptr(), ws.data_ptr(),
+                                 ws.numel(), stream), "dp_region_outlines")
+    return plan
+
+
+def simplify_outlines(plan: dict, max_polygon_vertices: int = 1 << 18, resolution: Optional[float] = None,
+                      min_area: Optional[float] = None) -> dict:
+    """The reference's `approximate_contour` on the outlines of `region_outlines` (`dp_simplify_outlines`, rules S1-S7
+    of the header): area filter (`min_area` / 4), epsilon = 0.005 * perimeter, closed Douglas-Peucker, `is_valid`, the
+    rectangle snap.  `resolution` and `min_area` default to the plan's parameters.  Adds to `plan` and returns it:
+    `polygon_offsets` (max_regions + 1,) int32, `polygon_vertices` (max_polygon_vertices, 2) float64 in grid units,
+    `polygons` (max_regions, 8) float64 in `POLYGON_COLUMNS` order -- one row per region, `drop_reason` indexing
+    `DROP_REASONS` -- and `polygon_stats` (8,) float64 in `POLYGON_STATS` order.  Asynchronous, no read-back.
+    Stated difference: OpenCV's final clean-up pass of `approxPolyDP` is not built."""
+    mp = _check_capacity("max_polygon_vertices", max_polygon_vertices)
+    keys = ("outline_offsets", "outline_vertices", "outline_columns", "outline_measures", "n_regions", "table")
+    if isinstance(plan, dict) and "outline_offsets" not in plan and "labels" in plan:
+        raise ValueError("plan holds no outlines: call region_outlines first")
+    lib, dev, mr, stream = _plan_args(plan, keys)
+    params = plan.get("parameters", {})
+    res = float(params["resolution"] if resolution is None else resolution)
+    area = float(params["min_area"] if min_area is None else min_area)
+    _check_floor(res, min_area=area)
+    mv = int(plan["outline_vertices"].shape[0])
+    ws = torch.empty(int(lib.dp_outline_workspace_size(0, mr, mv)), dtype=torch.uint8, device=dev)
+    plan["polygon_offsets"] = torch.zeros(mr + 1, dtype=torch.int32, device=dev)
+    plan["polygon_vertices"] = torch.empty(mp, 2, dtype=torch.float64, device=dev)
+    plan["polygons"] = torch.zeros(mr, len(POLYGON_COLUMNS), dtype=torch.float64, device=dev)
+    plan["polygon_stats"] = torch.empty(8, dtype=torch.float64, device=dev)
+    check(lib.dp_simplify_outlines(plan["outline_offsets"].data_ptr(), plan["outline_vertices"].data_ptr(),
+                                   plan["outline_columns"].data_ptr(), plan["outline_measures"].data_ptr(),
+                                   plan["n_regions"].data_ptr(), mr, mv, res, area, mp, plan["polygon_offsets"].data_ptr(),
+                                   plan["polygon_vertices"].data_ptr(), plan["polygons"].data_ptr(),
+                                   plan["polygon_stats"].data_ptr(), ws.data_ptr(), ws.numel(), stream), "dp_simplify_outlines")
+    return plan
+
+
+def floor_mean_height(points: torch.Tensor, count=None, height_threshold: Optional[float] = 1.3) -> torch.Tensor:
+    """(2,) float64 on the device: the mean y of the raster's participants (the finite rows with y >= the threshold;
+    None or NaN: every finite row) and their number -- the height label of the reference's polygons file
+    (`create_height_slices`).  Without participants the mean is the threshold.  Asynchronous, no read-back."""
+    thr = float("nan") if height_threshold is None else float(height_threshold)
+    _check_floor(height_threshold=thr)
+    lib, pts, n, count, cptr, stream = _points_args(points, count, _OUTLINE)
+    out = torch.empty(2, dtype=torch.float64, device=pts.device)
+    check(lib.dp_floor_mean_height(pts.data_ptr(), cptr, n, thr, out.data_ptr(), stream), "dp_floor_mean_height")
+    return out
+
+
+def floor_polygons(plan: dict, points: Optional[torch.Tensor] = None, count=None, max_vertices: int = 1 << 20,
+                   max_polygon_vertices: int = 1 << 18) -> dict:
+    """`region_outlines`, then `simplify_outlines`, on a `floor_plan` result; with `points` (the cloud the plan was made
+    from) also `mean_height` (`floor_mean_height` with the plan's threshold).  Returns `plan` with their tensors added;
+    all on the device, nothing synchronised."""
+    _check_capacity("max_vertices", max_vertices)
+    _check_capacity("max_polygon_vertices", max_polygon_vertices)
+    region_outlines(plan, max_vertices)
+    simplify_outlines(plan, max_polygon_vertices)
+    if points is not None:
+        plan["mean_height"] = floor_mean_height(points, count, plan["parameters"]["height_threshold"])
+    return plan
+
+
+def reference_world(xy: np.ndarray, origin, resolution: float) -> np.ndarray:
+    """Grid-unit vertices as the reference's file holds them: `shapely.affinity.scale` with its default origin scales
+    about the centre of the polygon's bounding box (in grid units), then the grid origin is added."""
+    xy = np.asarray(xy, dtype=np.float64).reshape(-1, 2)
+    cx = (xy[:, 0].min() + xy[:, 0].max()) / 2.0
+    cy = (xy[:, 1].min() + xy[:, 1].max()) / 2.0
+    return np.stack([cx + (xy[:, 0] - cx) * resolution + origin[0], cy + (xy[:, 1] - cy) * resolution + origin[1]], axis=1)
+
+
+def floor_polygons_summary(plan: dict) -> dict:
+    """The `{base}_floorplan_polygons.json` content from a `floor_polygons` result: the one read-back (it synchronises
+    the current stream).  {"origin", "resolution", "height" (the mean height of the participants; the threshold when the
+    plan has no `mean_height`), "participants", "parameters", "outline_stats", "polygon_stats", "polygons": one object
+    per kept polygon in label order -- label, snapped, flags, area_cells, area, epsilon, outline_vertices,
+    vertices_grid, vertices (origin + x * resolution) and vertices_reference (the reference file's arithmetic) --,
+    "dropped": [{label, reason}]}.  JSON-serialisable."""
+    if "polygons" not in plan or "polygon_offsets" not in plan:
+        raise ValueError("plan holds no polygons: call floor_polygons first")
+    params = plan["parameters"]
+    mean = plan.get("mean_height")
+    small = torch.cat([plan["origin"], plan["outline_stats"], plan["polygon_stats"], plan["n_regions"].to(torch.float64),
+                       mean if mean is not None else torch.zeros(2, dtype=torch.float64, device=plan["origin"].device)]
+                      ).cpu().numpy()
+    origin = [float(small[0]), float(small[1])]
+    res = params["resolution"]
+    rows = min(max(int(small[18]), 0), plan["polygons"].shape[0])
+    pol = plan["polygons"][:rows].cpu().numpy()
+    off = plan["polygon_offsets"][:rows + 1].cpu().numpy()
+    verts = plan["polygon_vertices"][:int(off[rows]) if rows else 0].cpu().numpy()
+    thr = params.get("height_threshold")
+    height = float(small[19]) if mean is not None else (float(thr) if thr is not None else 0.0)
+    polygons, dropped = [], []
+    for r, row in enumerate(pol):
+        if row[6] != 0 or row[1] < 1:
+            dropped.append({"label": r + 1, "reason": DROP_REASONS[int(row[6])]})
+            continue
+        xy = verts[off[r]:off[r + 1]]
+        polygons.append({"label": r + 1, "snapped": bool(int(row[2]) & POLYGON_SNAPPED), "flags": int(row[2]),
+                         "area_cells": float(row[3]), "area": float(row[4]), "epsilon": float(row[5]),
+                         "outline_vertices": int(row[7]), "vertices_grid": xy.tolist(),
+                         "vertices": (np.asarray(origin) + xy * res).tolist(),
+                         "vertices_reference": reference_world(xy, origin, res).tolist()})
+    return {"origin": origin, "resolution": res, "height": height,
+            "participants": int(small[20]) if mean is not None else None, "parameters": dict(params),
+            "outline_stats": {k: float(v) for k, v in zip(OUTLINE_STATS, small[2:10])},
+            "polygon_stats": {k: float(v) for k, v in zip(POLYGON_STATS, small[10:18])}, "polygons": polygons,
+            "dropped": dropped}
+
+
+def export_floorplan_text(path: str, summary: dict) -> str:
+    """The reference's `{base}_floorplan.txt` (`save_floorplan_data`) from a `floor_polygons_summary`: its five header
+    lines, then one line per polygon, `height, n, x1, z1, ...` with three decimals, in the reference's coordinates
+    (`vertices_reference`).  All heights are equal, so the reference's stable sort keeps OpenCV's contour order, which
+    is last-found first: descending label."""
+    lines = ["# Floor Plan Data\n", "# Units: meters\n\n", "# Shapes by height\n",
+             "# Format: height, num_points, x1, z1, x2, z2, ...\n"]
+    height = summary["height"]
+    for p in sorted(summary["polygons"], key=lambda q: -q["label"]):
+        xy = p["vertices_reference"]
+        lines.append(f"{height:.3f}, {len(xy)}" + "".join(f", {x:.3f}, {z:.3f}" for x, z in xy) + "\n")
+    tmp = path + ".tmp"
+    with open(tmp, "w") as f:
+        f.write("".join(lines))
+    os.replace(tmp, path)
+    return path
 
 
 GROUND_JSON = "ground.json"

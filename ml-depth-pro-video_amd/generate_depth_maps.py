@@ -308,7 +308,8 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                               cluster_height=1.3, cluster_max_points=100000, fit_shapes=False,
                               circularity_threshold=0.85, mesh_points=False, voxel_size=0.05, normals_max_nn=30,
                               floor_plan=False, floor_resolution=0.1, floor_height=1.3, floor_min_area=0.025,
-                              boundary_dir=None, split_l_shapes=False, simple_mesh=False, mesh_neighbors=6):
+                              boundary_dir=None, split_l_shapes=False, simple_mesh=False, mesh_neighbors=6,
+                              floor_polygons=False):
     """Directory loop (reference :153-206), pipelined decode -> GPU -> encode, frame-sharded across ranks.
 
     Every rank writes its own frames' files; each frame has exactly one owner.  resume=True skips
@@ -353,6 +354,10 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
     normals over radius 2 * voxel_size and at most normals_max_nn neighbours, oriented towards the origin)
     and writes `{base}_oriented.ply` (double x y z nx ny nz + uchar rgb) and `{base}_oriented.json`
     (parameters, point count, both statistics).
+    floor_polygons=True (implies floor_plan) traces the outline of every region of that plan, simplifies it as the
+    reference's `approximate_contour` does (`PC.floor_polygons`) and writes the reference's polygons file
+    `{base}_floorplan.txt` (`PC.export_floorplan_text`) and `{base}_floorplan_polygons.json` (every polygon in grid
+    units and in both world coordinates, flags, areas, and why a region has none).
     simple_mesh=True (implies mesh_points) meshes those voxels as the reference's `--mesh_method simple` does
     (`PC.triangulate`: every voxel's mesh_neighbors nearest others, the fan of triangles over them, degenerate and
     duplicated triangles removed) and writes `{base}_mesh.ply` (the vertices of `{base}_oriented.ply` without normals,
@@ -669,8 +674,10 @@ def _write_shapes(base: str, params: dict, out: dict) -> None:
 def _queue_floor(frame: dict, p: dict) -> dict:
     """The occupancy floor plan of the cleaned cloud (--floor_plan): raster, morphology, regions and picture, all left
     on the device (the grid's size is not known on the host yet); the writer makes the one read-back after the event."""
-    return PC.floor_plan(frame["xyz"], frame["cols"], frame["count"], height_threshold=p["height_threshold"],
+    plan = PC.floor_plan(frame["xyz"], frame["cols"], frame["count"], height_threshold=p["height_threshold"],
                          resolution=p["resolution"], min_area=p["min_area"])
+    frame["floor"] = plan                                                      # what --floor_polygons outlines
+    return plan
 
 
 def _write_floorplan(base: str, params: dict, out: dict) -> None:
@@ -686,6 +693,24 @@ def _write_floorplan(base: str, params: dict, out: dict) -> None:
     # no participants, or a grid past the capacity: a 1 x 1 white picture
     (Image.fromarray(img, "RGB") if img.size else Image.new("RGB", (1, 1), (255, 255, 255))).save(base + "_floorplan.png")
     with open(base + "_floorplan.json", "w") as f:
+        json.dump(summary, f, indent=1)
+
+
+def _queue_polygons(frame: dict, p: dict) -> dict:
+    """The polygons of the floor plan the floor stage has left on the device (--floor_polygons): outlines,
+    simplification, the mean height of the participants; the writer makes the one read-back after the event."""
+    return PC.floor_polygons(dict(frame["floor"]), frame["xyz"], frame["count"])
+
+
+def _write_polygons(base: str, params: dict, out: dict) -> None:
+    """Writer-thread side (after the frame's event): the one read-back on a stream of this thread's own, then
+    `{base}_floorplan.txt` (the reference's polygons file) and `{base}_floorplan_polygons.json`."""
+    plan = out["polygons"]
+    side = torch.cuda.Stream(plan["polygons"].device)
+    with torch.cuda.stream(side):
+        summary = PC.floor_polygons_summary(plan)
+    PC.export_floorplan_text(base + "_floorplan.txt", summary)
+    with open(base + "_floorplan_polygons.json", "w") as f:
         json.dump(summary, f, indent=1)
 
 
@@ -885,6 +910,8 @@ STAGES = (
           _queue_trimesh, _write_trimesh),
     Stage("boundary", None, lambda o: o["boundary_dir"] is not None, _boundary_params, ("_boundary.json",),
           _boundary, _write_boundary, _report_boundary),
+    Stage("polygons", "floor", lambda o: o["floor_polygons"], lambda o: {}, ("_floorplan.txt", "_floorplan_polygons.json"),
+          _queue_polygons, _write_polygons),
 )
 _DEFAULTS = {k: p.default for k, p in inspect.signature(batch_generate_depth_maps).parameters.items() if p.default is not p.empty}
 
@@ -945,7 +972,7 @@ def main():
                         help="Voxel edge of --mesh_points in metres (default 0.05); normals use radius 2 * voxel_size")
     parser.add_argument("--normals_max_nn", type=int, default=30,
                         help=f"Neighbours at the most per normal (1..{PC.MAX_NN}, default 30)")
-    # the two options below are passed on only when given: a run without them passes the keywords it always passed
+    # the two options below (and --floor_polygons) are passed on only when given: a run without them passes the keywords it always passed
     parser.add_argument("--simple_mesh", action="store_true", default=argparse.SUPPRESS,
                         help="Mesh the voxels of --mesh_points (which it implies) as the reference's --mesh_method simple "
                              "does: nearest neighbours, a fan of triangles, clean-up; {frame}_mesh.ply and {frame}_mesh.json")
@@ -959,6 +986,9 @@ def main():
                         help="Rasterise the points with y >= this height in metres (default 1.3; nan: every height)")
     parser.add_argument("--floor_min_area", type=float, default=0.025,
                         help="Draw the regions of at least this area in square metres (default 0.025)")
+    parser.add_argument("--floor_polygons", action="store_true", default=argparse.SUPPRESS,
+                        help="Trace and simplify the outline of every region of --floor_plan (which it implies), as the "
+                             "reference's approximate_contour does: {frame}_floorplan.txt and {frame}_floorplan_polygons.json")
     parser.add_argument("--boundary_dir", type=str, default=None,
                         help="Score each frame against DIR/{frame}.npy with the Depth Pro boundary metric (float32: a depth, "
                              "SI_boundary_F1; bool / uint8: a mask, SI_boundary_Recall); writes {frame}_boundary.json")
@@ -966,7 +996,8 @@ def main():
                         help="Skip frames whose {frame}_depth.png (with --clean_pointcloud: and {frame}_clean.ply; with "
                              "--cluster_pointcloud: and {frame}_clusters.json; with --fit_shapes: and {frame}_shapes.json; with "
                              "--mesh_points: and {frame}_oriented.ply / .json; with --simple_mesh: and {frame}_mesh.ply / .json; "
-                             "with --floor_plan: and {frame}_floorplan.png / .json; with "
+                             "with --floor_plan: and {frame}_floorplan.png / .json; with --floor_polygons: and {frame}_floorplan.txt / "
+                             "_floorplan_polygons.json; with "
                              "--boundary_dir, for a frame with a target: and {frame}_boundary.json) already exists in --output_dir")
     parser.add_argument("--colormap", type=str, default="turbo",
                         choices=["turbo", "viridis", "plasma", "inferno", "magma", "cividis", "jet"],

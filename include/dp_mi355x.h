@@ -1182,7 +1182,8 @@ int dp_floorplan_image(const int32_t* labels, const int32_t* dims, int32_t max_c
  *   and, after one workgroup has scanned the counts into offsets, once more to write.
  *
  * Simplification (dp_simplify_outlines), for each row r in turn; the reference runs in height-threshold
- * mode, so its own halvings apply.  polygons_out fp64 [max_regions][DP_POLYGON_COLUMNS] has one row per
+ * mode, so its own halvings apply (the default mode without a threshold, with the halvings undone, is
+ * dp_simplify_outlines_with and the section "Height-sliced floor plan" below).  polygons_out fp64 [max_regions][DP_POLYGON_COLUMNS] has one row per
  * region whether it keeps a polygon or not.
  *   S1. Area filter.  area * (resolution * resolution) < min_area / 4: no polygon (drop reason 1).  The
  *       reference divides min_area by 4 twice; the caller's min_area is after the first division.
@@ -1254,6 +1255,117 @@ int dp_simplify_outlines(const int32_t* offsets, const int32_t* vertices, const 
                          int64_t workspace_bytes, dp_stream_t stream);
 int dp_floor_mean_height(const double* points, const int32_t* n_dev, int32_t n_max, double height_threshold,
                          double* mean_out, dp_stream_t stream);
+
+/*
+ * ---- Height-sliced floor plan (additive to ABI 20, csrc/dp_slices.hip, csrc/dp_outline.hip) ----------
+ * The default mode of the reference's cleaned_pointcloud_to_floorplan.py, the one its CLI runs without
+ * --height_threshold: create_height_slices (:149-170) cuts the levelled cloud into num_slices bands,
+ * process_height_slice (:245-312) rasters each band at 0.05 m, closes it ONCE with a kernel whose size
+ * get_optimal_closing_kernel_size (:214-243) derives from the raw grid, opens it 3 x 3, and
+ * approximate_contour runs with alpha and min_area undivided.  The floor-plan sections' conventions hold:
+ * fp64 points [n_max][3] with a device count n_dev (NULL: n_max; clamped to [0, n_max]), everything on the
+ * caller's stream with no synchronisation and no host read-back, each fp64 operation rounded on its own (no
+ * FMA), argument errors returned as DP_ERR_* before any launch, no kernel waits on another workgroup,
+ * every loop is bounded by a count known when it starts, buffers have the caller's capacity and nothing is
+ * written past it.  The block is additive: no existing entry point, layout or output changes, and
+ * DP_ABI_VERSION stays 20.
+ * Layout.  S = num_slices in [1, DP_SLICE_MAX].  Every per-cell buffer is [S][max_cells], max_cells the
+ * capacity PER SLICE, S * max_cells <= 2^31 - 1 (else DP_ERR_SHAPE): slice s begins at the host-known
+ * offset s * max_cells.  Its live size is dims[s] = (H, W), a device int32 [S][2]; its origin is
+ * origin[s], a device fp64 [S][2].  So the stages behind the morphology are the existing entry points
+ * (dp_grid_regions, dp_region_outlines, dp_simplify_outlines_with) called per slice on offset pointers.
+ *   workspace  >= dp_slices_workspace_size(num_slices, max_cells) bytes of device memory, 8-byte aligned,
+ *              owned by the call until the stream has passed it (content need not be initialised): about
+ *              4.3 bytes per cell of all slices.  The three calls take the same size.
+ *
+ * Slice raster (dp_slice_grids): the grids of all S slices in two passes over the cloud.
+ *   R1. Bounds, in fp64, as the reference writes them: h = (height_max - height_min) / S,
+ *       lo_s = height_min + s * h, hi_s = lo_s + h, mid_s = (lo_s + hi_s) / 2.  bounds_out fp64 [S][3] =
+ *       (lo_s, hi_s, mid_s).  height_min and height_max finite, height_max > height_min (else DP_ERR_SHAPE).
+ *   R2. The participants of slice s are the finite live rows with y >= lo_s && y < hi_s, each slice's
+ *       pair of comparisons evaluated on its own.  hi_s and lo_{s+1} may differ in the last bit, so a row
+ *       may belong to two adjacent slices or to none, as in the reference; membership is never derived
+ *       from one division.
+ *   R3. Per slice, rules 2 to 5 of "Occupancy floor plan" with that slice's participants: minimum and
+ *       maximum of x and z, padding, W and H by ceil, the cell by truncation, a row with gx >= W or gz >= H
+ *       dropped and counted.  density_out uint32, height_out float32 (the largest (float)y of a cell's
+ *       members, 0 in an empty cell, -0.0 counts as +0.0), occupied_out uint8; no colour output.
+ *   R4. stats_out fp64 [S][8]: participants, dropped rows, occupied cells, H, W, status, 0, 0.  Status 1:
+ *       fewer than min_points participants (the reference: 10), or none at all; the slice is skipped and
+ *       its origin is (0, 0).  Status 2: W or H exceeds DP_FLOOR_MAX_DIM, or W * H > max_cells.  Under
+ *       either status dims[s] = (0, 0) and no cell of that slice is written; the other slices are
+ *       unaffected.  min_points < 0, resolution not finite or <= 0, padding not finite or < 0: DP_ERR_SHAPE.
+ *   Method: pass 1 takes a row per lane and, for each slice with a row in the wave, reduces the keys of
+ *   those rows over the wave (wave_minmax of dp_points.h); one lane adds the result to the workgroup's copy
+ *   in LDS and the workgroup issues one set of global atomics per slice it has seen.  One thread per slice
+ *   writes origin and dims.  Pass 2 is the raster's joining loop with the key (slice, cell): the slices
+ *   present in a wave are taken one after the other, so two rows with the same x and z in different slices
+ *   are never joined, and a row of two slices is rastered into both.  Without a colour there is no owner
+ *   row, so the cell's key is the 32 ordered bits of (float)y, kept in height_out between pass 2 and the
+ *   kernel that turns keys into heights.
+ *
+ * Closing sizes (dp_slice_closing_sizes), from the RAW binary grids (occupied_out, or any uint8 grids of
+ * this layout, non-zero = set):
+ *   C1. cells_s = the number of set cells of slice s; comps_s = the number of its 8-connected components
+ *       (what skimage.measure.label counts by default on a 2-D array; scipy.ndimage.label with a 3 x 3
+ *       structure of ones).  counts_out int64 [S][2] = (cells_s, comps_s).
+ *   C2. close_size_out int32 [S]:  3 if comps_s == 0 or cells_s < 400 * comps_s, else 5 if cells_s <
+ *       900 * comps_s, else 7 if cells_s < 1600 * comps_s, else 9 if cells_s < 2500 * comps_s, else 11.
+ *       This is the reference's max(3, min(11, int(sqrt(mean) / 5))), made odd by adding 1, in exact 64-bit
+ *       integers: int(sqrt(a) / 5) >= m holds exactly when cells >= 25 m^2 comps, and the mean's distance
+ *       from such a threshold is 0 or at least 1 / comps, far above fp64's rounding, so no device sqrt is
+ *       involved and nothing is within a tolerance (tests/test_slices.py pins the equivalence).
+ *   Method: the union-find of dp_points.h over the stacked cell index s * max_cells + c, each set cell joined
+ *   to its west, north-west, north and north-east neighbours inside its slice's dims; after the last union a
+ *   cell is a root iff it is its own parent, and the roots are counted with one ballot and one atomic per
+ *   wave (a wave's cells share their slice).  No table is built.
+ *
+ * Morphology with device sizes (dp_slice_morphology): rules 7 and 8 of "Occupancy floor plan" for all S
+ * slices in one call.
+ *   M1. The closing size of slice s is read ON THE DEVICE from close_size[s] (dp_slice_closing_sizes'
+ *       output); a value that is not odd or not in [1, DP_FLOOR_MAX_KERNEL] is read as 1 (the identity).
+ *   M2. close_iters (>= 0) and open_size (odd, in [1, DP_FLOOR_MAX_KERNEL]) are host values, else
+ *       DP_ERR_SHAPE; the reference uses 1 and 3.  grid_out may be grid.
+ *   Method: dp_grid_morphology's packed row and column passes with the slice in the launch grid's second
+ *   dimension and the radius looked up per slice.  dp_grid_morphology itself is unchanged.
+ *
+ * Simplification parameters (dp_simplify_outlines_with, csrc/dp_outline.hip): dp_simplify_outlines, rule for
+ * rule, with S1 and S2 taking their constants from the caller:
+ *   S1'. area * (resolution * resolution) < area_floor: no polygon (drop reason 1).
+ *   S2'. epsilon = alpha * perimeter.
+ *   area_floor and alpha finite and >= 0 (else DP_ERR_SHAPE).  dp_simplify_outlines(min_area) is
+ *   dp_simplify_outlines_with(min_area / 4, 0.005), bit for bit (a division by 4 is exact).  The default
+ *   mode passes the reference's (0.1, 0.01).
+ *
+ * The polygons file of all slices (Python: export_sliced_floorplan_text) is save_floorplan_data's: one line
+ * per kept polygon labelled with its slice's mid_s, slices in ascending height (the reference's sort is
+ * stable and the slices arrive in ascending order), within a slice descending label (OpenCV lists contours
+ * last-found first), coordinates as "Floor-plan polygons" states them.
+ * Not built: plot_floorplan, its viridis colours and the combined background grid (they feed only the
+ * plot); the reference's RANSAC floor plane (the cloud is already levelled by the ground stage); OpenCV's
+ * final clean-up pass inside approxPolyDP (still unstated: S3's stated difference); random thinning;
+ * batching the per-slice region, outline and simplify launches into one launch each (DESIGN.md section 19
+ * has what the per-slice launches cost).
+ */
+#define DP_SLICE_MAX 32
+int64_t dp_slices_workspace_size(int64_t num_slices, int64_t max_cells);
+int dp_slice_grids(const double* points, const int32_t* n_dev, int32_t n_max, double height_min, double height_max,
+                   int32_t num_slices, double resolution, double padding, int32_t min_points, int32_t max_cells,
+                   uint32_t* density_out, float* height_out, uint8_t* occupied_out, int32_t* dims_out,
+                   double* origin_out, double* bounds_out, double* stats_out, void* workspace,
+                   int64_t workspace_bytes, dp_stream_t stream);
+int dp_slice_closing_sizes(const uint8_t* grid, const int32_t* dims, int32_t num_slices, int32_t max_cells,
+                           int32_t* close_size_out, int64_t* counts_out, void* workspace, int64_t workspace_bytes,
+                           dp_stream_t stream);
+int dp_slice_morphology(const uint8_t* grid, const int32_t* dims, int32_t num_slices, int32_t max_cells,
+                        const int32_t* close_size, int32_t close_iters, int32_t open_size, uint8_t* grid_out,
+                        void* workspace, int64_t workspace_bytes, dp_stream_t stream);
+int dp_simplify_outlines_with(const int32_t* offsets, const int32_t* vertices, const int64_t* columns,
+                              const double* measures, const int32_t* n_regions_dev, int32_t max_regions,
+                              int32_t max_vertices, double resolution, double area_floor, double alpha,
+                              int32_t max_polygon_vertices, int32_t* polygon_offsets_out, double* polygon_vertices_out,
+                              double* polygons_out, double* stats_out, void* workspace, int64_t workspace_bytes,
+                              dp_stream_t stream);
 
 /*
  * ---- L-shape split (additive to ABI 20, csrc/dp_lshape.hip) -----------------------------------------

@@ -26,20 +26,6 @@ struct Hdr {
 };
 enum { C_PART = 0, C_NONFINITE, C_BELOW, C_DROPPED, C_OCCUPIED, C_ERR, C_FG };
 
-// H, W as every later stage reads them: anything outside [0, MAX_DIM] or beyond the capacity is no grid
-__device__ __forceinline__ void grid_dims(const int32_t* dims, int max_cells, int& H, int& W) {
-  H = dims[0]; W = dims[1];
-  if (H < 0 || W < 0 || H > MAX_DIM || W > MAX_DIM || (long long)H * W > max_cells) { H = 0; W = 0; }
-}
-
-// float32 -> order-preserving 32 bits (-0.0 folded onto +0.0) and back
-__device__ __forceinline__ uint32_t okey32(float v) {
-  uint32_t b = __float_as_uint(v);
-  if (v == 0.0f) b = 0;
-  return (b >> 31) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float unkey32(uint32_t k) { return __uint_as_float((k >> 31) ? (k & 0x7fffffffu) : ~k); }
-
 // ---- raster ---------------------------------------------------------------------------------------
 __global__ void hdr_init_kernel(Hdr* h) {
   for (int a = 0; a < 2; ++a) { h->mm[2 * a] = ~0ull; h->mm[2 * a + 1] = 0; }
@@ -81,12 +67,6 @@ __global__ void __launch_bounds__(256) minmax_xz_kernel(const double* __restrict
     if (bad) atomicAdd(&h->ctr[C_NONFINITE], bad);
     if (low) atomicAdd(&h->ctr[C_BELOW], low);
   }
-}
-
-// cells along one axis: (int)ceil(((max + padding) - min) / resolution), or -1 for more than MAX_DIM (NaN included)
-__device__ __forceinline__ int axis_cells(double mn, double mx_padded, double res) {
-  const double c = __builtin_ceil((mx_padded - mn) / res);
-  return c >= 0.0 && c <= (double)MAX_DIM ? (int)c : -1;
 }
 
 __global__ void grid_setup_kernel(Hdr* h, double res, double padding, int max_cells, int32_t* dims, double* origin) {
@@ -204,7 +184,6 @@ __global__ void grid_stats_kernel(const Hdr* h, double* st) {
 // ---- morphology -----------------------------------------------------------------------------------
 // A row is packed 64 cells to a word, bit i of word j = cell 64 j + i; the bits past W in a row's last
 // word are kept 0.  One wave packs one word: the ballot of "my cell is set".
-__device__ __forceinline__ u64 tail_mask(int W) { return (W & 63) ? ((1ull << (W & 63)) - 1) : ~0ull; }
 
 __global__ void __launch_bounds__(256) pack_kernel(const uint8_t* __restrict__ grid, const int32_t* dims, int max_cells,
                                                    u64* __restrict__ bits) {

@@ -24,11 +24,6 @@ constexpr int PCOLS = DP_POLYGON_COLUMNS;
 constexpr uint32_t NO_CELL = ~0u;
 typedef long long i64;
 
-__device__ __forceinline__ void grid_dims(const int32_t* dims, int max_cells, int& H, int& W) {
-  H = dims[0]; W = dims[1];
-  if (H < 0 || W < 0 || H > MAX_DIM || W > MAX_DIM || (long long)H * W > max_cells) { H = 0; W = 0; }
-}
-
 // direction d of rule O2 (0 = E, counter-clockwise on the screen, z down) as a step: two bits per direction
 __device__ __forceinline__ int dir_dx(int d) { return (int)((0x901Au >> (2 * d)) & 3u) - 1; }
 __device__ __forceinline__ int dir_dz(int d) { return (int)((0xA901u >> (2 * d)) & 3u) - 1; }
@@ -241,7 +236,7 @@ struct PolyWs {
 __global__ void __launch_bounds__(HULL_NT) simplify_kernel(const int32_t* __restrict__ offsets, const int32_t* __restrict__ vertices,
                                                            const i64* __restrict__ cols, const double* __restrict__ real,
                                                            const int32_t* n_regions, int max_regions, int max_vertices,
-                                                           double resolution, double min_area, PolyWs w,
+                                                           double resolution, double area_floor, double alpha, PolyWs w,
                                                            double* __restrict__ pcols) {
   __shared__ HullLds s;
   __shared__ u64 smax;
@@ -254,13 +249,13 @@ __global__ void __launch_bounds__(HULL_NT) simplify_kernel(const int32_t* __rest
     const long long beg = offsets[r], end = offsets[r + 1];
     const bool have = nv64 > 0 && beg >= 0 && end <= max_vertices && end - beg == nv64;
     const int nv = have ? (int)nv64 : 0;
-    const double area = real[(size_t)r * RCOLS], eps = 0.005 * real[(size_t)r * RCOLS + 1];
+    const double area = real[(size_t)r * RCOLS], eps = alpha * real[(size_t)r * RCOLS + 1];
     const double eps2 = eps * eps;
     const int32_t* V = vertices + 2 * (have ? beg : 0);
     const long long wb = (have ? beg : 0) + r;                   // nv + 1 workspace entries from here
     int reason = DROP_NONE, m = 0, snapped = 0;
     double parea = 0.0;
-    if (area * (resolution * resolution) < min_area / 4.0) reason = DROP_SMALL;            // S1
+    if (area * (resolution * resolution) < area_floor) reason = DROP_SMALL;                // S1
     else if (!have) reason = DROP_OVERFLOW;
     int A = 0;
     if (!reason) {
@@ -569,29 +564,41 @@ extern "C" int dp_region_outlines(const int32_t* labels, const int32_t* dims, in
   return 0;
 }
 
-extern "C" int dp_simplify_outlines(const int32_t* offsets, const int32_t* vertices, const int64_t* columns, const double* measures,
-                                    const int32_t* n_regions_dev, int32_t max_regions, int32_t max_vertices, double resolution,
-                                    double min_area, int32_t max_polygon_vertices, int32_t* polygon_offsets_out,
-                                    double* polygon_vertices_out, double* polygons_out, double* stats_out, void* workspace,
-                                    int64_t workspace_bytes, dp_stream_t stream) {
+extern "C" int dp_simplify_outlines_with(const int32_t* offsets, const int32_t* vertices, const int64_t* columns,
+                                         const double* measures, const int32_t* n_regions_dev, int32_t max_regions,
+                                         int32_t max_vertices, double resolution, double area_floor, double alpha,
+                                         int32_t max_polygon_vertices, int32_t* polygon_offsets_out, double* polygon_vertices_out,
+                                         double* polygons_out, double* stats_out, void* workspace, int64_t workspace_bytes,
+                                         dp_stream_t stream) {
   if (!offsets || !n_regions_dev || !polygon_offsets_out || !stats_out || (max_vertices > 0 && !vertices) ||
       (max_polygon_vertices > 0 && !polygon_vertices_out) || (max_regions > 0 && (!columns || !measures || !polygons_out)))
     return DP_ERR_ARG;
-  if (max_regions < 0 || max_vertices < 0 || max_polygon_vertices < 0 || !pos_finite(resolution) || !(min_area >= 0.0) ||
-      !(min_area < __builtin_inf()))
+  if (max_regions < 0 || max_vertices < 0 || max_polygon_vertices < 0 || !pos_finite(resolution) || !(area_floor >= 0.0) ||
+      !(area_floor < __builtin_inf()) || !(alpha >= 0.0) || !(alpha < __builtin_inf()))
     return DP_ERR_SHAPE;
   Ws w;
   if (!ws_carve(workspace, workspace_bytes, max_regions, max_vertices, &w)) return DP_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   const int gr = region_grid(max_regions);
   hipLaunchKernelGGL(simplify_kernel, dim3(gr), dim3(HULL_NT), 0, s, offsets, vertices, (const i64*)columns, measures, n_regions_dev,
-                     max_regions, max_vertices, resolution, min_area, w.p, polygons_out);
+                     max_regions, max_vertices, resolution, area_floor, alpha, w.p, polygons_out);
   hipLaunchKernelGGL(poly_offsets_kernel, dim3(1), dim3(256), 0, s, w.p, n_regions_dev, max_regions, max_polygon_vertices,
                      polygon_offsets_out, polygons_out, stats_out);
   hipLaunchKernelGGL(poly_write_kernel, dim3(gr), dim3(64), 0, s, offsets, vertices, w.p, n_regions_dev, max_regions, max_vertices,
                      max_polygon_vertices, polygon_offsets_out, polygons_out, polygon_vertices_out);
   DP_CHECK_LAUNCH();
   return 0;
+}
+
+// the height-threshold mode's halvings (S1: min_area / 4, an exact division, so a bad min_area stays one; S2: alpha 0.01 / 2)
+extern "C" int dp_simplify_outlines(const int32_t* offsets, const int32_t* vertices, const int64_t* columns, const double* measures,
+                                    const int32_t* n_regions_dev, int32_t max_regions, int32_t max_vertices, double resolution,
+                                    double min_area, int32_t max_polygon_vertices, int32_t* polygon_offsets_out,
+                                    double* polygon_vertices_out, double* polygons_out, double* stats_out, void* workspace,
+                                    int64_t workspace_bytes, dp_stream_t stream) {
+  return dp_simplify_outlines_with(offsets, vertices, columns, measures, n_regions_dev, max_regions, max_vertices, resolution,
+                                   min_area / 4.0, 0.005, max_polygon_vertices, polygon_offsets_out, polygon_vertices_out,
+                                   polygons_out, stats_out, workspace, workspace_bytes, stream);
 }
 
 extern "C" int dp_floor_mean_height(const double* points, const int32_t* n_dev, int32_t n_max, double height_threshold,

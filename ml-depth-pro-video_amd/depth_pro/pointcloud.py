@@ -1516,6 +1516,30 @@ def region_outlines(plan: dict, max_vertices: int = 1 << 20) -> dict:
     return plan
 
 
+def _simplify(plan: dict, max_polygon_vertices: int, resolution: Optional[float], call) -> dict:
+    """The part `simplify_outlines` and `simplify_outlines_with` share: checks, the output tensors, and `call(lib, head,
+    res, tail)` with the entry point's arguments in front of and behind its own parameters."""
+    mp = _check_capacity("max_polygon_vertices", max_polygon_vertices)
+    keys = ("outline_offsets", "outline_vertices", "outline_columns", "outline_measures", "n_regions", "table")
+    if isinstance(plan, dict) and "outline_offsets" not in plan and "labels" in plan:
+        raise ValueError("plan holds no outlines: call region_outlines first")
+    lib, dev, mr, stream = _plan_args(plan, keys)
+    res = float(plan.get("parameters", {})["resolution"] if resolution is None else resolution)
+    _check_floor(res)
+    mv = int(plan["outline_vertices"].shape[0])
+    ws = torch.empty(int(lib.dp_outline_workspace_size(0, mr, mv)), dtype=torch.uint8, device=dev)
+    plan["polygon_offsets"] = torch.zeros(mr + 1, dtype=torch.int32, device=dev)
+    plan["polygon_vertices"] = torch.empty(mp, 2, dtype=torch.float64, device=dev)
+    plan["polygons"] = torch.zeros(mr, len(POLYGON_COLUMNS), dtype=torch.float64, device=dev)
+    plan["polygon_stats"] = torch.empty(8, dtype=torch.float64, device=dev)
+    head = (plan["outline_offsets"].data_ptr(), plan["outline_vertices"].data_ptr(), plan["outline_columns"].data_ptr(),
+            plan["outline_measures"].data_ptr(), plan["n_regions"].data_ptr(), mr, mv, res)
+    tail = (mp, plan["polygon_offsets"].data_ptr(), plan["polygon_vertices"].data_ptr(), plan["polygons"].data_ptr(),
+            plan["polygon_stats"].data_ptr(), ws.data_ptr(), ws.numel(), stream)
+    call(lib, head, tail)
+    return plan
+
+
 def simplify_outlines(plan: dict, max_polygon_vertices: int = 1 << 18, resolution: Optional[float] = None,
                       min_area: Optional[float] = None) -> dict:
     """The reference's `approximate_contour` on the outlines of `region_outlines` (`dp_simplify_outlines`, rules S1-S7
@@ -1525,27 +1549,28 @@ def simplify_outlines(plan: dict, max_polygon_vertices: int = 1 << 18, resolutio
     `polygons` (max_regions, 8) float64 in `POLYGON_COLUMNS` order -- one row per region, `drop_reason` indexing
     `DROP_REASONS` -- and `polygon_stats` (8,) float64 in `POLYGON_STATS` order.  Asynchronous, no read-back.
     Stated difference: OpenCV's final clean-up pass of `approxPolyDP` is not built."""
-    mp = _check_capacity("max_polygon_vertices", max_polygon_vertices)
-    keys = ("outline_offsets", "outline_vertices", "outline_columns", "outline_measures", "n_regions", "table")
+    _check_capacity("max_polygon_vertices", max_polygon_vertices)
     if isinstance(plan, dict) and "outline_offsets" not in plan and "labels" in plan:
         raise ValueError("plan holds no outlines: call region_outlines first")
-    lib, dev, mr, stream = _plan_args(plan, keys)
-    params = plan.get("parameters", {})
-    res = float(params["resolution"] if resolution is None else resolution)
-    area = float(params["min_area"] if min_area is None else min_area)
-    _check_floor(res, min_area=area)
-    mv = int(plan["outline_vertices"].shape[0])
-    ws = torch.empty(int(lib.dp_outline_workspace_size(0, mr, mv)), dtype=torch.uint8, device=dev)
-    plan["polygon_offsets"] = torch.zeros(mr + 1, dtype=torch.int32, device=dev)
-    plan["polygon_vertices"] = torch.empty(mp, 2, dtype=torch.float64, device=dev)
-    plan["polygons"] = torch.zeros(mr, len(POLYGON_COLUMNS), dtype=torch.float64, device=dev)
-    plan["polygon_stats"] = torch.empty(8, dtype=torch.float64, device=dev)
-    check(lib.dp_simplify_outlines(plan["outline_offsets"].data_ptr(), plan["outline_vertices"].data_ptr(),
-                                   plan["outline_columns"].data_ptr(), plan["outline_measures"].data_ptr(),
-                                   plan["n_regions"].data_ptr(), mr, mv, res, area, mp, plan["polygon_offsets"].data_ptr(),
-                                   plan["polygon_vertices"].data_ptr(), plan["polygons"].data_ptr(),
-                                   plan["polygon_stats"].data_ptr(), ws.data_ptr(), ws.numel(), stream), "dp_simplify_outlines")
-    return plan
+    if not isinstance(plan, dict):
+        raise ValueError("plan must be a floor_plan result")
+    area = float(plan.get("parameters", {})["min_area"] if min_area is None else min_area)
+    _check_floor(min_area=area)
+    return _simplify(plan, max_polygon_vertices, resolution, lambda lib, head, tail: check(
+        lib.dp_simplify_outlines(*head, area, *tail), "dp_simplify_outlines"))
+
+
+def simplify_outlines_with(plan: dict, area_floor: float, alpha: float, max_polygon_vertices: int = 1 << 18,
+                           resolution: Optional[float] = None) -> dict:
+    """`simplify_outlines` with the two constants of rules S1 and S2 given by the caller (`dp_simplify_outlines_with`):
+    a region is dropped when its outline's area in m^2 is below `area_floor`, and epsilon = `alpha` * perimeter.
+    `simplify_outlines(min_area)` is `(min_area / 4, 0.005)`, the reference's height-threshold mode; its default mode
+    is `(0.1, 0.01)`.  Same outputs; asynchronous, no read-back."""
+    for name, v in (("area_floor", area_floor), ("alpha", alpha)):
+        if not (np.isfinite(float(v)) and float(v) >= 0):
+            raise ValueError(f"{name} must be finite and >= 0 (got {v})")
+    return _simplify(plan, max_polygon_vertices, resolution, lambda lib, head, tail: check(
+        lib.dp_simplify_outlines_with(*head, float(area_floor), float(alpha), *tail), "dp_simplify_outlines_with"))
 
 
 def floor_mean_height(points: torch.Tensor, count=None, height_threshold: Optional[float] = 1.3) -> torch.Tensor:
@@ -1634,6 +1659,184 @@ def export_floorplan_text(path: str, summary: dict) -> str:
     for p in sorted(summary["polygons"], key=lambda q: -q["label"]):
         xy = p["vertices_reference"]
         lines.append(f"{height:.3f}, {len(xy)}" + "".join(f", {x:.3f}, {z:.3f}" for x, z in xy) + "\n")
+    tmp = path + ".tmp"
+    with open(tmp, "w") as f:
+        f.write("".join(lines))
+    os.replace(tmp, path)
+    return path
+
+
+# ---- height-sliced floor plan: slices, adaptive closing, polygons (csrc/dp_slices.hip) -----------------
+
+SLICE_STATS = ("participants", "dropped", "occupied_cells", "height", "width", "status", "reserved0", "reserved1")
+SLICE_STATUS = ("ok", "too_few_points", "too_large")
+SLICE_MAX = _lib.DP_SLICE_MAX
+
+_SLICES = "the height-sliced floor plan runs on the ROCm device (csrc/dp_slices.hip)"
+
+
+def _check_slices(num_slices, max_cells, height_min=0.0, height_max=1.0, min_points=0) -> Tuple[int, int]:
+    s, mc = int(num_slices), int(max_cells)
+    if not 1 <= s <= SLICE_MAX:
+        raise ValueError(f"num_slices must be in [1, {SLICE_MAX}] (got {num_slices})")
+    if mc < 0 or s * mc >= 2 ** 31:
+        raise ValueError("max_cells must be >= 0 with num_slices * max_cells <= 2^31 - 1")
+    if not (np.isfinite(float(height_min)) and np.isfinite(float(height_max)) and float(height_max) > float(height_min)):
+        raise ValueError(f"height_min and height_max must be finite with height_max > height_min (got {height_min}, {height_max})")
+    if int(min_points) < 0:
+        raise ValueError(f"min_points must be >= 0 (got {min_points})")
+    return s, mc
+
+
+def _stack_args(grid: torch.Tensor, dims: torch.Tensor):
+    """(lib, contiguous (S, max_cells) grid, S, max_cells, stream) of a stage over stacked slice grids."""
+    if grid.device.type != "cuda":
+        raise _lib.DPError(_SLICES)
+    if grid.dtype != torch.uint8 or grid.dim() != 2:
+        raise ValueError("grid must be a (num_slices, max_cells) uint8 tensor")
+    s, mc = _check_slices(grid.shape[0], grid.shape[1])
+    if not torch.is_tensor(dims) or dims.device != grid.device or dims.dtype != torch.int32 or tuple(dims.shape) != (s, 2) or \
+            not dims.is_contiguous():
+        raise ValueError("dims must be a contiguous device int32 tensor (num_slices, 2) on the grid's device")
+    return _lib.load(), grid.contiguous(), s, mc, torch.cuda.current_stream(grid.device).cuda_stream
+
+
+def slice_grids(points: torch.Tensor, count=None, height_min: float = 0.1, height_max: float = 2.5, num_slices: int = 5,
+                resolution: float = 0.05, padding: float = 0.5, min_points: int = 10, max_cells: int = 1 << 20) -> dict:
+    """The grids of all height slices of the levelled cloud in two passes over it (`dp_slice_grids`, rules R1-R4 of the
+    header): the reference's `create_height_slices` and the raster of `process_height_slice`.  Slice s holds the finite
+    rows with lo_s <= y < hi_s; each has its own bounds, grid and origin.  Returns a dict of device tensors, S =
+    `num_slices`: `density` (S, max_cells) int32 holding the uint32 counts, `height` (S, max_cells) float32, `occupied`
+    (S, max_cells) uint8, `dims` (S, 2) int32 (H, W), `origin` (S, 2) float64, `bounds` (S, 3) float64 (lo, hi, mid),
+    `stats` (S, 8) float64 in `SLICE_STATS` order.  `max_cells` is the capacity per slice; row s of a per-cell tensor is
+    slice s, its first H * W entries the grid.  status 1: fewer than `min_points` rows, 2: the grid would exceed
+    `max_cells`; such a slice has dims (0, 0) and the others are unaffected.  Asynchronous, no read-back."""
+    s, mc = _check_slices(num_slices, max_cells, height_min, height_max, min_points)
+    _check_floor(resolution, padding)
+    lib, pts, n, count, cptr, stream = _points_args(points, count, _SLICES)
+    dev = pts.device
+    ws = torch.empty(int(lib.dp_slices_workspace_size(s, mc)), dtype=torch.uint8, device=dev)
+    out = {"density": torch.empty(s, mc, dtype=torch.int32, device=dev), "height": torch.empty(s, mc, dtype=torch.float32, device=dev),
+           "occupied": torch.empty(s, mc, dtype=torch.uint8, device=dev), "dims": torch.empty(s, 2, dtype=torch.int32, device=dev),
+           "origin": torch.empty(s, 2, dtype=torch.float64, device=dev), "bounds": torch.empty(s, 3, dtype=torch.float64, device=dev),
+           "stats": torch.empty(s, 8, dtype=torch.float64, device=dev)}
+    check(lib.dp_slice_grids(pts.data_ptr(), cptr, n, float(height_min), float(height_max), s, float(resolution), float(padding),
+                             int(min_points), mc, out["density"].data_ptr(), out["height"].data_ptr(), out["occupied"].data_ptr(),
+                             out["dims"].data_ptr(), out["origin"].data_ptr(), out["bounds"].data_ptr(), out["stats"].data_ptr(),
+                             ws.data_ptr(), ws.numel(), stream), "dp_slice_grids")
+    return out
+
+
+def slice_closing_sizes(grid: torch.Tensor, dims: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The closing size each slice's raw binary grid asks for (`dp_slice_closing_sizes`, rules C1-C2): the reference's
+    `get_optimal_closing_kernel_size` -- the mean size of the 8-connected components picks 3, 5, 7, 9 or 11 -- as an
+    exact integer rule.  `grid` (S, max_cells) uint8 and `dims` (S, 2) are `slice_grids`' `occupied` and `dims`.
+    Returns (close_size (S,) int32, counts (S, 2) int64 = set cells, components) on the device; no read-back."""
+    lib, g, s, mc, stream = _stack_args(grid, dims)
+    ws = torch.empty(int(lib.dp_slices_workspace_size(s, mc)), dtype=torch.uint8, device=g.device)
+    size = torch.empty(s, dtype=torch.int32, device=g.device)
+    counts = torch.empty(s, 2, dtype=torch.int64, device=g.device)
+    check(lib.dp_slice_closing_sizes(g.data_ptr(), dims.data_ptr(), s, mc, size.data_ptr(), counts.data_ptr(), ws.data_ptr(),
+                                     ws.numel(), stream), "dp_slice_closing_sizes")
+    return size, counts
+
+
+def slice_morphology(grid: torch.Tensor, dims: torch.Tensor, close_size: torch.Tensor, close_iters: int = 1, open_size: int = 3,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`grid_morphology` for all slices in one call, the closing size of slice s read on the device from `close_size`
+    (S,) int32 (`dp_slice_morphology`); a size that is not odd or not in [1, 15] acts as 1.  `close_iters` closings,
+    then one opening by `open_size` -- the reference's default mode with (1, 3).  Returns a 0 / 1 grid (S, max_cells)
+    (`out=grid`: in place).  Asynchronous, no read-back."""
+    _check_floor(close_iters=close_iters, open_size=open_size)
+    lib, g, s, mc, stream = _stack_args(grid, dims)
+    if not torch.is_tensor(close_size) or close_size.device != g.device or close_size.dtype != torch.int32 or \
+            close_size.numel() != s or not close_size.is_contiguous():
+        raise ValueError("close_size must be a contiguous device int32 tensor of num_slices entries on the grid's device")
+    if out is None:
+        out = torch.empty_like(g)
+    elif out.dtype != torch.uint8 or out.device != g.device or tuple(out.shape) != (s, mc) or not out.is_contiguous():
+        raise ValueError("out must be a contiguous uint8 tensor of the grid's shape on its device")
+    ws = torch.empty(int(lib.dp_slices_workspace_size(s, mc)), dtype=torch.uint8, device=g.device)
+    check(lib.dp_slice_morphology(g.data_ptr(), dims.data_ptr(), s, mc, close_size.data_ptr(), int(close_iters), int(open_size),
+                                  out.data_ptr(), ws.data_ptr(), ws.numel(), stream), "dp_slice_morphology")
+    return out
+
+
+def sliced_floor_plan(points: torch.Tensor, count=None, height_min: float = 0.1, height_max: float = 2.5, num_slices: int = 5,
+                      resolution: float = 0.05, padding: float = 0.5, min_points: int = 10, min_area: float = 0.1,
+                      alpha: float = 0.01, open_size: int = 3, max_cells: int = 1 << 20, max_regions: int = 4096,
+                      max_vertices: int = 1 << 20, max_polygon_vertices: int = 1 << 18) -> dict:
+    """The default mode of the reference's `cleaned_pointcloud_to_floorplan.py` (no height threshold): `slice_grids`,
+    `slice_closing_sizes` and `slice_morphology` once for all slices, then per slice, on the views of its rows,
+    `grid_regions`, `region_outlines` and `simplify_outlines_with(min_area, alpha)` -- one closing of the adaptive size,
+    one opening, alpha and min_area undivided.  Returns `slice_grids`' dict with `close_size`, `counts`, `cleaned`,
+    `parameters` and `slices` added: a list of one plan dict per slice with the keys `floor_plan`, `region_outlines`
+    and `simplify_outlines` use.  Every slice runs every stage (its status is only known on the device; a skipped slice
+    has an empty grid and no regions).  All tensors on the device, nothing synchronised."""
+    _check_slices(num_slices, max_cells, height_min, height_max, min_points)
+    _check_floor(resolution, padding, max_cells=max_cells, open_size=open_size, min_area=min_area, max_regions=max_regions)
+    if not (np.isfinite(float(alpha)) and float(alpha) >= 0):
+        raise ValueError(f"alpha must be finite and >= 0 (got {alpha})")
+    _check_capacity("max_vertices", max_vertices)
+    _check_capacity("max_polygon_vertices", max_polygon_vertices)
+    out = slice_grids(points, count, height_min, height_max, num_slices, resolution, padding, min_points, max_cells)
+    out["close_size"], out["counts"] = slice_closing_sizes(out["occupied"], out["dims"])
+    out["cleaned"] = slice_morphology(out["occupied"], out["dims"], out["close_size"], 1, open_size)
+    out["parameters"] = {"height_min": float(height_min), "height_max": float(height_max), "num_slices": int(num_slices),
+                         "resolution": float(resolution), "padding": float(padding), "min_points": int(min_points),
+                         "min_area": float(min_area), "alpha": float(alpha), "close_iters": 1, "open_size": int(open_size)}
+    out["slices"] = []
+    for s in range(int(num_slices)):
+        plan = {k: out[k][s] for k in ("density", "height", "occupied", "cleaned", "dims", "origin")}
+        plan["parameters"] = {"resolution": float(resolution), "min_area": float(min_area), "alpha": float(alpha),
+                              "height_threshold": None}
+        plan["labels"], plan["n_regions"], plan["table"], plan["region_stats"] = grid_regions(
+            plan["cleaned"], plan["dims"], plan["density"], plan["height"], plan["origin"], resolution, max_regions)
+        region_outlines(plan, max_vertices)
+        simplify_outlines_with(plan, min_area, alpha, max_polygon_vertices)
+        out["slices"].append(plan)
+    return out
+
+
+def sliced_floor_plan_summary(plan: dict) -> dict:
+    """The `{base}_floorslices.json` content from a `sliced_floor_plan` result: the read-back (it synchronises the
+    current stream).  {"resolution", "parameters", "slices": one object per slice in ascending height -- index, lo, hi,
+    height (the slice's mid height, the label of its polygons), participants, dropped_rows, occupied_cells, status
+    (`SLICE_STATUS`), grid [H, W], origin, set_cells, components, close_size, region_stats, and `floor_polygons_summary`'s
+    outline_stats, polygon_stats, polygons and dropped}.  JSON-serialisable."""
+    if "slices" not in plan or "bounds" not in plan:
+        raise ValueError("plan holds no slices: call sliced_floor_plan first")
+    n = len(plan["slices"])
+    small = torch.cat([plan["bounds"].reshape(-1), plan["stats"].reshape(-1), plan["origin"].reshape(-1),
+                       plan["counts"].to(torch.float64).reshape(-1), plan["close_size"].to(torch.float64)]).cpu().numpy()
+    bounds, stats = small[:3 * n].reshape(n, 3), small[3 * n:11 * n].reshape(n, 8)
+    origin, counts, sizes = small[11 * n:13 * n].reshape(n, 2), small[13 * n:15 * n].reshape(n, 2), small[15 * n:16 * n]
+    slices = []
+    for s, sub in enumerate(plan["slices"]):
+        p = floor_polygons_summary(sub)
+        slices.append({"index": s, "lo": float(bounds[s, 0]), "hi": float(bounds[s, 1]), "height": float(bounds[s, 2]),
+                       "participants": int(stats[s, 0]), "dropped_rows": int(stats[s, 1]), "occupied_cells": int(stats[s, 2]),
+                       "status": SLICE_STATUS[int(stats[s, 5])], "grid": [int(stats[s, 3]), int(stats[s, 4])],
+                       "origin": [float(origin[s, 0]), float(origin[s, 1])], "set_cells": int(counts[s, 0]),
+                       "components": int(counts[s, 1]), "close_size": int(sizes[s]),
+                       "region_stats": {k: float(v) for k, v in zip(REGION_STATS, sub["region_stats"].cpu().numpy())},
+                       "outline_stats": p["outline_stats"], "polygon_stats": p["polygon_stats"], "polygons": p["polygons"],
+                       "dropped": p["dropped"]})
+    return {"resolution": plan["parameters"]["resolution"], "parameters": dict(plan["parameters"]), "slices": slices}
+
+
+def export_sliced_floorplan_text(path: str, summary: dict) -> str:
+    """The reference's floor-plan file (`save_floorplan_data`) for all slices, from a `sliced_floor_plan_summary`: the
+    five header lines, then one line per kept polygon, `height, n, x1, z1, ...` with three decimals, labelled with its
+    slice's mid height, in the reference's coordinates (`vertices_reference`).  Slices in ascending height (the
+    reference's sort is stable and the slices arrive in ascending order); within a slice descending label, as
+    `export_floorplan_text` and for the same reason.  Written through a temporary file and `os.replace`."""
+    lines = ["# Floor Plan Data\n", "# Units: meters\n\n", "# Shapes by height\n",
+             "# Format: height, num_points, x1, z1, x2, z2, ...\n"]
+    for sl in sorted(summary["slices"], key=lambda q: q["index"]):
+        for p in sorted(sl["polygons"], key=lambda q: -q["label"]):
+            xy = p["vertices_reference"]
+            lines.append(f"{sl['height']:.3f}, {len(xy)}" + "".join(f", {x:.3f}, {z:.3f}" for x, z in xy) + "\n")
     tmp = path + ".tmp"
     with open(tmp, "w") as f:
         f.write("".join(lines))

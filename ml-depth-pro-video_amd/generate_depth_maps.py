@@ -309,7 +309,8 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                               circularity_threshold=0.85, mesh_points=False, voxel_size=0.05, normals_max_nn=30,
                               floor_plan=False, floor_resolution=0.1, floor_height=1.3, floor_min_area=0.025,
                               boundary_dir=None, split_l_shapes=False, simple_mesh=False, mesh_neighbors=6,
-                              floor_polygons=False):
+                              floor_polygons=False, floor_slices=0, floor_slice_min=0.1, floor_slice_max=2.5,
+                              floor_slice_resolution=0.05, floor_slice_min_area=0.1):
     """Directory loop (reference :153-206), pipelined decode -> GPU -> encode, frame-sharded across ranks.
 
     Every rank writes its own frames' files; each frame has exactly one owner.  resume=True skips
@@ -358,6 +359,12 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
     reference's `approximate_contour` does (`PC.floor_polygons`) and writes the reference's polygons file
     `{base}_floorplan.txt` (`PC.export_floorplan_text`) and `{base}_floorplan_polygons.json` (every polygon in grid
     units and in both world coordinates, flags, areas, and why a region has none).
+    floor_slices=N (N > 0; implies clean_pointcloud) makes the reference's default floor plan, the one without a height
+    threshold (`PC.sliced_floor_plan`): N height slices between floor_slice_min and floor_slice_max, each rasterised at
+    floor_slice_resolution, closed once with the size its raw grid asks for, opened 3 x 3, outlined and simplified with
+    alpha 0.01 and floor_slice_min_area undivided; writes `{base}_floorslices.txt` (the reference's polygons file, every
+    polygon labelled with its slice's mid height) and `{base}_floorslices.json` (per slice: bounds, counts, status, grid,
+    closing size, polygons).
     simple_mesh=True (implies mesh_points) meshes those voxels as the reference's `--mesh_method simple` does
     (`PC.triangulate`: every voxel's mesh_neighbors nearest others, the fan of triangles over them, degenerate and
     duplicated triangles removed) and writes `{base}_mesh.ply` (the vertices of `{base}_oriented.ply` without normals,
@@ -521,6 +528,17 @@ def check_floor(resolution, height, min_area) -> None:
         raise ValueError(f"--floor_height must be finite, or nan for every height (got {height})")
     if not (np.isfinite(float(min_area)) and float(min_area) >= 0):
         raise ValueError(f"--floor_min_area must be finite and >= 0 (got {min_area})")
+
+
+def check_floor_slices(num_slices, height_min, height_max, resolution, min_area) -> None:
+    if not 1 <= int(num_slices) <= PC.SLICE_MAX:
+        raise ValueError(f"--floor_slices must be in [1, {PC.SLICE_MAX}] (got {num_slices})")
+    if not (np.isfinite(float(height_min)) and np.isfinite(float(height_max)) and float(height_max) > float(height_min)):
+        raise ValueError(f"--floor_slice_min and --floor_slice_max must be finite with max > min (got {height_min}, {height_max})")
+    if not (np.isfinite(float(resolution)) and float(resolution) > 0):
+        raise ValueError(f"--floor_slice_resolution must be finite and > 0 (got {resolution})")
+    if not (np.isfinite(float(min_area)) and float(min_area) >= 0):
+        raise ValueError(f"--floor_slice_min_area must be finite and >= 0 (got {min_area})")
 
 
 def check_boundary_dir(boundary_dir) -> None:
@@ -714,6 +732,26 @@ def _write_polygons(base: str, params: dict, out: dict) -> None:
         json.dump(summary, f, indent=1)
 
 
+def _queue_slices(frame: dict, p: dict) -> dict:
+    """The height-sliced floor plan of the cleaned cloud (--floor_slices): the slices' grids, closing sizes and
+    morphology in one call each, then regions, outlines and polygons per slice, all left on the device; the writer makes
+    the read-back after the event."""
+    return PC.sliced_floor_plan(frame["xyz"], frame["count"], height_min=p["height_min"], height_max=p["height_max"],
+                                num_slices=p["num_slices"], resolution=p["resolution"], min_area=p["min_area"])
+
+
+def _write_slices(base: str, params: dict, out: dict) -> None:
+    """Writer-thread side (after the frame's event): the read-back on a stream of this thread's own, then
+    `{base}_floorslices.txt` (the reference's polygons file over all slices) and `{base}_floorslices.json`."""
+    plan = out["slices"]
+    side = torch.cuda.Stream(plan["stats"].device)
+    with torch.cuda.stream(side):
+        summary = PC.sliced_floor_plan_summary(plan)
+    PC.export_sliced_floorplan_text(base + "_floorslices.txt", summary)
+    with open(base + "_floorslices.json", "w") as f:
+        json.dump(summary, f, indent=1)
+
+
 def _queue_mesh(frame: dict, p: dict) -> dict:
     """The oriented point set of the cleaned cloud (--mesh_points): voxel grid, normals, orientation, PLY records.  Only
     the voxel count and the statistics are copied here; the records stay on the device and the writer fetches `count`."""
@@ -866,6 +904,14 @@ def _floor_params(o: dict) -> dict:
             "min_area": float(o["floor_min_area"])}
 
 
+def _slices_params(o: dict) -> dict:
+    check_floor_slices(o["floor_slices"], o["floor_slice_min"], o["floor_slice_max"], o["floor_slice_resolution"],
+                       o["floor_slice_min_area"])
+    return {"num_slices": int(o["floor_slices"]), "height_min": float(o["floor_slice_min"]),
+            "height_max": float(o["floor_slice_max"]), "resolution": float(o["floor_slice_resolution"]),
+            "min_area": float(o["floor_slice_min_area"])}
+
+
 def _mesh_params(o: dict) -> dict:
     check_mesh(o["voxel_size"], o["normals_max_nn"])
     return {"voxel_size": float(o["voxel_size"]), "max_nn": int(o["normals_max_nn"])}
@@ -904,6 +950,8 @@ STAGES = (
           _queue_shapes, _write_shapes),
     Stage("floor", "clean", lambda o: o["floor_plan"], _floor_params, ("_floorplan.png", "_floorplan.json"),
           _queue_floor, _write_floorplan),
+    Stage("slices", "clean", lambda o: bool(o["floor_slices"]), _slices_params, ("_floorslices.txt", "_floorslices.json"),
+          _queue_slices, _write_slices),
     Stage("mesh", "clean", lambda o: o["mesh_points"], _mesh_params, ("_oriented.ply", "_oriented.json"),
           _queue_mesh, _write_oriented),
     Stage("trimesh", "mesh", lambda o: o["simple_mesh"], _trimesh_params, ("_mesh.ply", "_mesh.json"),
@@ -972,7 +1020,7 @@ def main():
                         help="Voxel edge of --mesh_points in metres (default 0.05); normals use radius 2 * voxel_size")
     parser.add_argument("--normals_max_nn", type=int, default=30,
                         help=f"Neighbours at the most per normal (1..{PC.MAX_NN}, default 30)")
-    # the two options below (and --floor_polygons) are passed on only when given: a run without them passes the keywords it always passed
+    # the two options below (and --floor_polygons, --floor_slices and its options) are passed on only when given: a run without them passes the keywords it always passed
     parser.add_argument("--simple_mesh", action="store_true", default=argparse.SUPPRESS,
                         help="Mesh the voxels of --mesh_points (which it implies) as the reference's --mesh_method simple "
                              "does: nearest neighbours, a fan of triangles, clean-up; {frame}_mesh.ply and {frame}_mesh.json")
@@ -989,6 +1037,18 @@ def main():
     parser.add_argument("--floor_polygons", action="store_true", default=argparse.SUPPRESS,
                         help="Trace and simplify the outline of every region of --floor_plan (which it implies), as the "
                              "reference's approximate_contour does: {frame}_floorplan.txt and {frame}_floorplan_polygons.json")
+    parser.add_argument("--floor_slices", type=int, default=argparse.SUPPRESS, metavar="N",
+                        help="Write the reference's default floor plan of the cleaned cloud (implies --clean_pointcloud): N "
+                             "height slices (the reference: 5), each with its own grid, a closing of the size its grid asks "
+                             "for, and polygons; {frame}_floorslices.txt and {frame}_floorslices.json")
+    parser.add_argument("--floor_slice_min", type=float, default=argparse.SUPPRESS,
+                        help="Lower end of the lowest slice of --floor_slices in metres (default 0.1)")
+    parser.add_argument("--floor_slice_max", type=float, default=argparse.SUPPRESS,
+                        help="Upper end of the highest slice of --floor_slices in metres (default 2.5)")
+    parser.add_argument("--floor_slice_resolution", type=float, default=argparse.SUPPRESS,
+                        help="Cell size of --floor_slices in metres (default 0.05)")
+    parser.add_argument("--floor_slice_min_area", type=float, default=argparse.SUPPRESS,
+                        help="Keep the polygons of --floor_slices of at least this area in square metres (default 0.1)")
     parser.add_argument("--boundary_dir", type=str, default=None,
                         help="Score each frame against DIR/{frame}.npy with the Depth Pro boundary metric (float32: a depth, "
                              "SI_boundary_F1; bool / uint8: a mask, SI_boundary_Recall); writes {frame}_boundary.json")
@@ -997,7 +1057,7 @@ def main():
                              "--cluster_pointcloud: and {frame}_clusters.json; with --fit_shapes: and {frame}_shapes.json; with "
                              "--mesh_points: and {frame}_oriented.ply / .json; with --simple_mesh: and {frame}_mesh.ply / .json; "
                              "with --floor_plan: and {frame}_floorplan.png / .json; with --floor_polygons: and {frame}_floorplan.txt / "
-                             "_floorplan_polygons.json; with "
+                             "_floorplan_polygons.json; with --floor_slices: and {frame}_floorslices.txt / .json; with "
                              "--boundary_dir, for a frame with a target: and {frame}_boundary.json) already exists in --output_dir")
     parser.add_argument("--colormap", type=str, default="turbo",
                         choices=["turbo", "viridis", "plasma", "inferno", "magma", "cividis", "jet"],

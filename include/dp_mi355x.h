@@ -1636,6 +1636,57 @@ int dp_mesh_clean_triangles(const int32_t* tri_in, const int32_t* t_dev, int32_t
                             int32_t* tri_out, int32_t* t_out_dev, double* stats_out, void* workspace,
                             int64_t workspace_bytes, dp_stream_t stream);
 
+/*
+ * ---- Depth-warped views (ABI 20, additive; csrc/dp_effects.hip) ----------------------------------------------
+ * The "3D effects" of the reference's OLD_SCRIPTS/depth_video_effect.py (3D_EFFECTS_README.md): the frames of its
+ * parallax video (:10-111) and its red-cyan anaglyph (:113-183), from an RGB image and its depth map, both on the
+ * device.  Everything on the caller's stream with no synchronisation and no host read-back; argument errors are
+ * returned as DP_ERR_* before any launch (a null pointer, an unknown kind, a workspace that is too small or not
+ * 4-byte aligned, bad_out not 8-byte aligned: DP_ERR_ARG; H or W outside [1, 16384], n_views outside
+ * [1, DP_WARP_MAX_VIEWS]: DP_ERR_SHAPE).
+ *   image      uint8 [H][W][3]          depth   float32 [H][W]
+ *   workspace  >= dp_effects_workspace_size() bytes of device memory, 4-byte aligned, owned by the call until the
+ *              stream has passed it (content need not be initialised)
+ * The device does only IEEE add, subtract, multiply, divide and conversions, every one rounded on its own (no FMA),
+ * so the bytes are those of NumPy >= 2 promotion (a Python float is weak, an np.float64 scalar is not):
+ *   1. dn = (depth - min) / (max - min), every step in float32; min and max over the whole map.
+ *   2. Maps, with x, y the integer pixel coordinates (per view descriptor {kind, a, b}, three doubles):
+ *      DP_WARP_SHIFT      map_x = double(x) + a * double(1f - dn), map_y = double(y) + b * double(1f - dn), in fp64
+ *                         (parallax `circle`: a = amplitude W cos t, b = amplitude H sin t; `swing`: a = amplitude W
+ *                         sin t, b = 0; t = 2 pi frame / total_frames; cos and sin stay on the host, in numpy)
+ *      DP_WARP_SHIFT_F32  map_x = double(x) + double(float32(a) * (1f - dn)), the product in float32; map_y = y; b is
+ *                         not looked at (the anaglyph's views: a = +separation W for the left, - for the right)
+ *      DP_WARP_ZOOM       map_x = double(x) + a * (double(x) - W / 2), map_y = double(y) + a * (double(y) - H / 2), in
+ *                         fp64, a = 1 - zoom_factor = 1 - (1.0 + amplitude sin t); the depth is not read
+ *      then clip(map_x, 0, W - 1), clip(map_y, 0, H - 1) and a cast to float32.
+ *   3. Sampling: cv2.remap(INTER_LINEAR) on 8-bit pixels with float32 maps, OpenCV 4.x's published fixed-point rule:
+ *      sx = rint_half_even(map_x * 32), ix = sx >> 5, fx = sx & 31, the same for y; the four weights
+ *      32 (32 - fx | fx) (32 - fy | fy) sum to 32768; the result is (sum of w p + 16384) >> 15.  A tap outside the image
+ *      counts as 0; after the clip it always has weight 0.  No cv2 binary was available to run against, so, as for
+ *      dp_resize_u8_cv, parity with a cv2 binary is unpinned: tests/effects_numpy.py restates these rules and is
+ *      checked against scipy.ndimage.map_coordinates.
+ *   4. Anaglyph: channel 0 of the left view, channels 1 and 2 of the right view.
+ * Stated differences from the reference:
+ *   a. out[y][x] = sample(image, map_x[y][x], map_y[y][x]).  The reference passes map_x.T, map_y.T to cv2.remap; what
+ *      it gets is the transpose of this image (and its video writer silently fails on a non-square frame).
+ *   b. Non-finite depth is undefined in the reference.  Here min and max are taken over the finite depths, and a pixel
+ *      whose map_x or map_y is not finite before the clip (NaN or inf depth; max == min, where dn = 0 / 0) is written
+ *      as (0, 0, 0) and counted in bad_out.  DP_WARP_ZOOM has no such pixels.
+ * dp_warp_views: views is a HOST array fp64 [n_views][3] (read during the call), out uint8 [n_views][H][W][3], bad_out
+ * device int64 [n_views].  The depth is read once per pixel for all views.
+ * dp_anaglyph: dx = separation * W (rounded to float32 here), out uint8 [H][W][3], bad_out device int64 [1]; one
+ * fused pass, no intermediate views.
+ */
+#define DP_WARP_MAX_VIEWS 32
+#define DP_WARP_SHIFT     0
+#define DP_WARP_SHIFT_F32 1
+#define DP_WARP_ZOOM      2
+int64_t dp_effects_workspace_size(void);
+int dp_warp_views(const uint8_t* image, const float* depth, int32_t H, int32_t W, const double* views, int32_t n_views,
+                  uint8_t* out, int64_t* bad_out, void* workspace, int64_t workspace_bytes, dp_stream_t stream);
+int dp_anaglyph(const uint8_t* image, const float* depth, int32_t H, int32_t W, double dx, uint8_t* out,
+                int64_t* bad_out, void* workspace, int64_t workspace_bytes, dp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,7 @@ import torch.distributed as dist
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import depth_pro  # noqa: E402  (this package's drop-in)
 from depth_pro import distributed as D  # noqa: E402
+from depth_pro import effects as FX  # noqa: E402
 from depth_pro import pointcloud as PC  # noqa: E402
 
 
@@ -245,6 +246,8 @@ oriented_json_name = partial(frame_file, suffix="_oriented.json")
 floorplan_name = partial(frame_file, suffix="_floorplan.png")           # --floor_plan; origin, statistics, regions beside it
 floorplan_json_name = partial(frame_file, suffix="_floorplan.json")
 boundary_name = partial(frame_file, suffix="_boundary.json")            # --boundary_dir: the score against `{base}.npy` there
+anaglyph_name = partial(frame_file, suffix="_anaglyph.png")             # --anaglyph
+parallax_name = partial(frame_file, suffix="_parallax.png")             # --parallax
 
 
 def cloud_name(image_path: str, cleaned: bool = False) -> str:
@@ -310,7 +313,8 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                               floor_plan=False, floor_resolution=0.1, floor_height=1.3, floor_min_area=0.025,
                               boundary_dir=None, split_l_shapes=False, simple_mesh=False, mesh_neighbors=6,
                               floor_polygons=False, floor_slices=0, floor_slice_min=0.1, floor_slice_max=2.5,
-                              floor_slice_resolution=0.05, floor_slice_min_area=0.1):
+                              floor_slice_resolution=0.05, floor_slice_min_area=0.1, anaglyph=False,
+                              anaglyph_separation=0.05, parallax=None, parallax_amplitude=0.05, parallax_period=150):
     """Directory loop (reference :153-206), pipelined decode -> GPU -> encode, frame-sharded across ranks.
 
     Every rank writes its own frames' files; each frame has exactly one owner.  resume=True skips
@@ -375,6 +379,15 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
     a float32 target is a depth (SI_boundary_F1), a bool or uint8 one a mask (SI_boundary_Recall, the raw values
     thresholded by > 0.1).  `{base}_boundary.json` holds the kind, the score, the per-threshold counts, the thresholds,
     H and W; a missing or unusable target is reported and the frame goes on without a score; rank 0 prints the mean.
+    anaglyph=True writes `{base}_anaglyph.png`, the reference's red-cyan anaglyph (OLD_SCRIPTS/depth_video_effect.py
+    :113-183) of the frame and its depth, both still on the device (`depth_pro.effects.anaglyph`, anaglyph_separation
+    as the reference's --separation), as RGB.
+    parallax="circle" | "zoom" | "swing" writes `{base}_parallax.png`, one frame of the reference's parallax video
+    (:10-111, `depth_pro.effects.warp_views`) with parallax_amplitude, at phase (the frame's position in the sorted
+    list of all frames) mod parallax_period of a parallax_period-frame cycle (150: the reference's 5 s x 30 fps): a
+    directory of parallax_period copies of one still reproduces the reference's video frame by frame, a real video
+    gets the camera motion laid over it; the phase does not depend on how the frames are dealt to the ranks.
+    Both report, in one line per frame, the pixels written black for want of a finite depth when there are any.
     """
     params = resolve_stages(**{k: v for k, v in locals().items() if k in _DEFAULTS}, output_dir=output_dir)
     on = [st for st in STAGES if st.name in params]
@@ -441,7 +454,7 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                         out["cloud"] = _points(depth, pred["focallength_px"], image)
                     else:
                         frame = {"depth": depth, "f_px": pred["focallength_px"], "image": image, "path": image_paths[k],
-                                 "world": world, "rank": rank}
+                                 "world": world, "rank": rank, "index": k}
                         for st in on:
                             out[st.name] = st.queue(frame, params[st.name])
                         if "cloud" in params:                 # the records of the cloud as the stages have left it
@@ -874,6 +887,44 @@ def _report_boundary(p: dict, world: int, rank: int) -> None:
         print(f"mean boundary score over {n} frames: {total / n:.6f}" if n else "no frame had a usable boundary target")
 
 
+def _frame_rgb(frame: dict) -> torch.Tensor:
+    """The frame's RGB image on the depth's device (uint8 (H, W, 3)), uploaded once for the stages that sample it."""
+    if "rgb" not in frame:
+        image = frame["image"]
+        rgb = image if torch.is_tensor(image) else torch.from_numpy(np.ascontiguousarray(image))
+        frame["rgb"] = rgb.to(frame["depth"].device, non_blocking=True)
+    return frame["rgb"]
+
+
+def _queue_anaglyph(frame: dict, p: dict) -> dict:
+    """The red-cyan anaglyph of the frame (--anaglyph): one fused pass over image and depth, then its pinned host copy."""
+    picture, bad = FX.anaglyph(_frame_rgb(frame), frame["depth"], p["separation"])
+    return {"image": _pinned(picture), "bad": _pinned(bad)}
+
+
+def _queue_parallax(frame: dict, p: dict) -> dict:
+    """The frame's view of the parallax cycle (--parallax) at phase `index mod period`, then its pinned host copy."""
+    h, w = frame["depth"].shape
+    view = FX.view_params(p["motion"], p["amplitude"], w, h, int(frame["index"]) % p["period"], p["period"])
+    pictures, bad = FX.warp_views(_frame_rgb(frame), frame["depth"], [view])
+    return {"image": _pinned(pictures[0]), "bad": _pinned(bad[0])}
+
+
+def _write_view(path: str, payload: dict) -> None:
+    """Writer-thread side (after the frame's event): the RGB PNG, and a line when pixels had no finite depth."""
+    _write_png(path, payload["image"].numpy())
+    if int(payload["bad"]):
+        print(f"{os.path.basename(path)}: {int(payload['bad'])} pixels without a finite depth written black")
+
+
+def _write_anaglyph(base: str, params: dict, out: dict) -> None:
+    _write_view(base + "_anaglyph.png", out["anaglyph"])
+
+
+def _write_parallax(base: str, params: dict, out: dict) -> None:
+    _write_view(base + "_parallax.png", out["parallax"])
+
+
 # ---- each stage's parameter dict from the loop's options `o`, checked first ----
 
 def _ground_params(o: dict) -> dict:
@@ -927,6 +978,30 @@ def _boundary_params(o: dict) -> dict:
     return {"dir": o["boundary_dir"], "scores": []}
 
 
+def check_anaglyph(separation) -> None:
+    if not (np.isfinite(float(separation)) and float(separation) >= 0):
+        raise ValueError(f"--anaglyph_separation must be finite and >= 0 (got {separation})")
+
+
+def check_parallax(motion, amplitude, period) -> None:
+    if motion not in FX.MOTIONS:
+        raise ValueError(f"--parallax must be one of {', '.join(FX.MOTIONS)} (got {motion})")
+    if not (np.isfinite(float(amplitude)) and float(amplitude) >= 0):
+        raise ValueError(f"--parallax_amplitude must be finite and >= 0 (got {amplitude})")
+    if int(period) < 1:
+        raise ValueError(f"--parallax_period must be >= 1 (got {period})")
+
+
+def _anaglyph_params(o: dict) -> dict:
+    check_anaglyph(o["anaglyph_separation"])
+    return {"separation": float(o["anaglyph_separation"])}
+
+
+def _parallax_params(o: dict) -> dict:
+    check_parallax(o["parallax"], o["parallax_amplitude"], o["parallax_period"])
+    return {"motion": o["parallax"], "amplitude": float(o["parallax_amplitude"]), "period": int(o["parallax_period"])}
+
+
 class Stage(NamedTuple):
     """One stage of the frame loop, described once."""
     name: str
@@ -958,6 +1033,9 @@ STAGES = (
           _queue_trimesh, _write_trimesh),
     Stage("boundary", None, lambda o: o["boundary_dir"] is not None, _boundary_params, ("_boundary.json",),
           _boundary, _write_boundary, _report_boundary),
+    Stage("anaglyph", None, lambda o: bool(o["anaglyph"]), _anaglyph_params, ("_anaglyph.png",), _queue_anaglyph, _write_anaglyph),
+    Stage("parallax", None, lambda o: o["parallax"] is not None, _parallax_params, ("_parallax.png",), _queue_parallax,
+          _write_parallax),
     Stage("polygons", "floor", lambda o: o["floor_polygons"], lambda o: {}, ("_floorplan.txt", "_floorplan_polygons.json"),
           _queue_polygons, _write_polygons),
 )
@@ -1020,7 +1098,7 @@ def main():
                         help="Voxel edge of --mesh_points in metres (default 0.05); normals use radius 2 * voxel_size")
     parser.add_argument("--normals_max_nn", type=int, default=30,
                         help=f"Neighbours at the most per normal (1..{PC.MAX_NN}, default 30)")
-    # the two options below (and --floor_polygons, --floor_slices and its options) are passed on only when given: a run without them passes the keywords it always passed
+    # the two options below (and --floor_polygons, --floor_slices, --anaglyph, --parallax and their options) are passed on only when given: a run without them passes the keywords it always passed
     parser.add_argument("--simple_mesh", action="store_true", default=argparse.SUPPRESS,
                         help="Mesh the voxels of --mesh_points (which it implies) as the reference's --mesh_method simple "
                              "does: nearest neighbours, a fan of triangles, clean-up; {frame}_mesh.ply and {frame}_mesh.json")
@@ -1049,6 +1127,17 @@ def main():
                         help="Cell size of --floor_slices in metres (default 0.05)")
     parser.add_argument("--floor_slice_min_area", type=float, default=argparse.SUPPRESS,
                         help="Keep the polygons of --floor_slices of at least this area in square metres (default 0.1)")
+    parser.add_argument("--anaglyph", action="store_true", default=argparse.SUPPRESS,
+                        help="Write {frame}_anaglyph.png, the red-cyan anaglyph of the frame and its depth (RGB)")
+    parser.add_argument("--anaglyph_separation", type=float, default=argparse.SUPPRESS,
+                        help="Separation between the left and the right view of --anaglyph (default 0.05; 0.01-0.1 recommended)")
+    parser.add_argument("--parallax", type=str, choices=list(FX.MOTIONS), default=argparse.SUPPRESS,
+                        help="Write {frame}_parallax.png, the frame seen from a camera moving through the reference's "
+                             "parallax cycle (circle, zoom or swing), at phase (frame position) mod --parallax_period")
+    parser.add_argument("--parallax_amplitude", type=float, default=argparse.SUPPRESS,
+                        help="Amplitude of the camera motion of --parallax (default 0.05; 0.01-0.2 recommended)")
+    parser.add_argument("--parallax_period", type=int, default=argparse.SUPPRESS,
+                        help="Frames per cycle of --parallax (default 150: 5 s at 30 frames/s)")
     parser.add_argument("--boundary_dir", type=str, default=None,
                         help="Score each frame against DIR/{frame}.npy with the Depth Pro boundary metric (float32: a depth, "
                              "SI_boundary_F1; bool / uint8: a mask, SI_boundary_Recall); writes {frame}_boundary.json")
@@ -1058,7 +1147,8 @@ def main():
                              "--mesh_points: and {frame}_oriented.ply / .json; with --simple_mesh: and {frame}_mesh.ply / .json; "
                              "with --floor_plan: and {frame}_floorplan.png / .json; with --floor_polygons: and {frame}_floorplan.txt / "
                              "_floorplan_polygons.json; with --floor_slices: and {frame}_floorslices.txt / .json; with "
-                             "--boundary_dir, for a frame with a target: and {frame}_boundary.json) already exists in --output_dir")
+                             "--boundary_dir, for a frame with a target: and {frame}_boundary.json; with --anaglyph: and "
+                             "{frame}_anaglyph.png; with --parallax: and {frame}_parallax.png) already exists in --output_dir")
     parser.add_argument("--colormap", type=str, default="turbo",
                         choices=["turbo", "viridis", "plasma", "inferno", "magma", "cividis", "jet"],
                         help="Colormap for depth visualization")

@@ -1687,6 +1687,79 @@ int dp_warp_views(const uint8_t* image, const float* depth, int32_t H, int32_t W
 int dp_anaglyph(const uint8_t* image, const float* depth, int32_t H, int32_t W, double dx, uint8_t* out,
                 int64_t* bad_out, void* workspace, int64_t workspace_bytes, dp_stream_t stream);
 
+/*
+ * ---- Depth shadows (ABI 20, additive; csrc/dp_shadows.hip) ---------------------------------------------------
+ * The image-space depth-shadow tools of the reference's OLD_SCRIPTS/mesh_from_depth.py: find_depth_shadows (:1110-1170)
+ * and the ground-plane fill of remove_depth_shadows (:1857-1944).  A depth map has no true value at a silhouette; the
+ * pixels between foreground and background back-project to a sheet of points behind every object.  Everything runs on
+ * the caller's stream as separate launches, with no synchronisation and no read-back.  Every entry point returns
+ * DP_ERR_ARG before any launch for: a null pointer (depth_out of dp_depth_shadows alone may be null), h or w < 1,
+ * h * w >= 2^31, a threshold_factor that is not finite, min_region_size < 0, a workspace that is null, not 8-byte
+ * aligned or shorter than dp_shadows_workspace_size(h, w) (which returns 0 for a size it refuses).
+ *   depth      float32 [h][w]      masks   uint8 [h][w] (0 / 1)      workspace   device memory, owned by the call until
+ *   the stream has passed it, content need not be initialised
+ *   stats_out  device fp64 [DP_SHADOW_STATS], written by every call (entries a call does not compute are 0):
+ *     EDGE         pixels that are not free (dp_depth_edges, dp_depth_shadows: edge pixels)
+ *     SHADOW       pixels of the output mask that are 1
+ *     COMPONENTS   4-connected free components        KEPT      those with >= min_region_size pixels
+ *     LARGEST      pixels of the largest component    GMAX      the gradient's maximum
+ *     NONFINITE    depth pixels that are NaN or inf   ERROR     1 when NONFINITE > 0, else 0
+ *     NONPOSITIVE  shadow pixels whose depth is <= 0 (dp_depth_shadows; the only pixels for which the reference goes on
+ *                  to its cKDTree nearest-valid fill, which is not built)
+ * dp_depth_gradient: np.sqrt(sobel(d, 1)**2 + sobel(d, 0)**2) with scipy.ndimage.sobel, bit for bit.  sobel on float32
+ *   is two 1-D passes with mode='reflect' (the sample beyond an edge is the edge sample; a length-1 axis sees itself
+ *   three times): the derivative [-1, 0, 1] along the axis, rounded to float32, then the smoothing [1, 2, 1] along the
+ *   other axis, rounded to float32.  Each pass accumulates in fp64 in scipy's order: centre * weight first, then
+ *   (left - right) * -1, or (left + right) * 1, added to it.  Then dx * dx, dy * dy, their sum and the square root in
+ *   float32, each rounded on its own (no FMA, correctly rounded square root).  gmax_out: device float32 [1], the
+ *   maximum over the frame (an atomicMax per workgroup on the bit pattern: non-negative floats order as integers).
+ * dp_depth_edges: edge = (gmax > 0 ? g / gmax : g) > float32(threshold_factor), division and comparison in float32,
+ *   the division correctly rounded (NumPy >= 2 compares a float32 array with a Python float in float32).  The reference's
+ *   depth_threshold = threshold_factor * depth_map.mean() is dead code and is not computed; its Canny branch (image is
+ *   not None) is not built, remove_depth_shadows never passes the image.
+ *   Non-finite depth is outside the contract and defined: it is counted (NONFINITE), and such a frame has no edges,
+ *   every pixel is free.  Nothing faults on it.
+ * dp_region_filter: free_mask is any uint8 [h][w] (non-zero = free).  mask_out is 1 where the pixel is not free or its
+ *   4-connected (scipy.ndimage.label's default cross, not the 3 x 3 square) free component has fewer than
+ *   min_region_size pixels: the reference's ~np.isin(labels, valid_regions).  No numbering is produced.
+ * dp_depth_shadows: the chain gradient, edges, region filter on ~edge.  depth_out, when not null, receives the depth
+ *   with the shadow pixels set to NaN (dp_depth_to_points drops those: its valid test is d == d && d > 0).  Dropping
+ *   them is this project's use of the mask; the reference fills them.
+ * dp_fill_ground_shadows: the reference's fill for shadow pixels (shadow != 0) in the rows >= int(ground_rows * h)
+ *   (the reference: 0.7), all in fp64 in the reference's evaluation order, stored rounded to float32; every other
+ *   pixel is copied.  plane is a HOST array fp64 [4] = {n0, n1, n2, d} of n . p + d = 0, in the frame the formula
+ *   assumes (camera axes, y down, unit normal; documented, not converted); cx = w / 2, cy = h / 2, f = max(w, h) are
+ *   the reference's choices here, not the camera's.
+ *     |n2| > 1e-6:                z = (-n0 x - n1 y - d) / n2 with x = (xi - cx) * 1.0 / f, y = (yi - cy) * 1.0 / f
+ *     else |n0| > 1e-6:           DP_ERR_ARG (the reference's 100-step depth search is not built)
+ *     else (horizontal plane):    z = (-d / n1) * f / den, den = yi - cy, replaced by 1e-6 where |den| < 1e-6
+ *     z = max(z, 0.1).  filled_out: device int64 [1] (8-byte aligned), the pixels filled.  A plane or ground_rows that
+ *     is not finite is DP_ERR_ARG.  No workspace.
+ * Not built: detect_ground_plane / optimize_ground_plane (RANSAC, scipy's optimiser) and the cKDTree fill.
+ */
+#define DP_SHADOW_STATS            9
+#define DP_SHADOW_STAT_EDGE        0
+#define DP_SHADOW_STAT_SHADOW      1
+#define DP_SHADOW_STAT_COMPONENTS  2
+#define DP_SHADOW_STAT_KEPT        3
+#define DP_SHADOW_STAT_LARGEST     4
+#define DP_SHADOW_STAT_GMAX        5
+#define DP_SHADOW_STAT_NONFINITE   6
+#define DP_SHADOW_STAT_ERROR       7
+#define DP_SHADOW_STAT_NONPOSITIVE 8
+int64_t dp_shadows_workspace_size(int32_t h, int32_t w);
+int dp_depth_gradient(const float* depth, int32_t h, int32_t w, float* grad_out, float* gmax_out, double* stats_out,
+                      void* workspace, int64_t workspace_bytes, dp_stream_t stream);
+int dp_depth_edges(const float* depth, int32_t h, int32_t w, double threshold_factor, uint8_t* edge_out,
+                   double* stats_out, void* workspace, int64_t workspace_bytes, dp_stream_t stream);
+int dp_region_filter(const uint8_t* free_mask, int32_t h, int32_t w, int32_t min_region_size, uint8_t* mask_out,
+                     double* stats_out, void* workspace, int64_t workspace_bytes, dp_stream_t stream);
+int dp_depth_shadows(const float* depth, int32_t h, int32_t w, double threshold_factor, int32_t min_region_size,
+                     uint8_t* mask_out, float* depth_out, double* stats_out, void* workspace, int64_t workspace_bytes,
+                     dp_stream_t stream);
+int dp_fill_ground_shadows(const float* depth, const uint8_t* shadow, int32_t h, int32_t w, const double* plane,
+                           double ground_rows, float* depth_out, int64_t* filled_out, dp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,7 @@ DP_OUTLINE_INT_COLUMNS, DP_OUTLINE_REAL_COLUMNS, DP_POLYGON_COLUMNS = 4, 2, 8
 DP_SLICE_MAX = 32
 DP_WARP_MAX_VIEWS, DP_WARP_MAX_DIM = 32, 16384
 DP_WARP_SHIFT, DP_WARP_SHIFT_F32, DP_WARP_ZOOM = 0, 1, 2
+DP_SHADOW_STATS = 9
 DP_ABI_VERSION = 20
 
 _ERRORS = {1000: "DP_ERR_ARG", 1001: "DP_ERR_SHAPE", 1002: "DP_ERR_ALIGN", 1003: "DP_ERR_DTYPE"}
@@ -65,6 +66,8 @@ EXPORTS = (
     "dp_outline_workspace_size", "dp_region_outlines", "dp_simplify_outlines", "dp_floor_mean_height",
     "dp_slices_workspace_size", "dp_slice_grids", "dp_slice_closing_sizes", "dp_slice_morphology", "dp_simplify_outlines_with",
     "dp_effects_workspace_size", "dp_warp_views", "dp_anaglyph",
+    "dp_shadows_workspace_size", "dp_depth_gradient", "dp_depth_edges", "dp_region_filter", "dp_depth_shadows",
+    "dp_fill_ground_shadows",
 )
 
 
@@ -197,6 +200,12 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "dp_effects_workspace_size": [],
         "dp_warp_views": [vp, vp, i32, i32, ctypes.POINTER(f64), i32, vp, vp, vp, i64, vp],
         "dp_anaglyph": [vp, vp, i32, i32, f64, vp, vp, vp, i64, vp],
+        "dp_shadows_workspace_size": [i32, i32],
+        "dp_depth_gradient": [vp, i32, i32, vp, vp, vp, vp, i64, vp],
+        "dp_depth_edges": [vp, i32, i32, f64, vp, vp, vp, i64, vp],
+        "dp_region_filter": [vp, i32, i32, i32, vp, vp, vp, i64, vp],
+        "dp_depth_shadows": [vp, i32, i32, f64, i32, vp, vp, vp, vp, i64, vp],
+        "dp_fill_ground_shadows": [vp, vp, i32, i32, ctypes.POINTER(f64), f64, vp, vp, vp],
     }
     for name, argtypes in sig.items():
         fn = getattr(lib, name)
@@ -215,6 +224,7 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.dp_outline_workspace_size.restype = ctypes.c_int64
     lib.dp_slices_workspace_size.restype = ctypes.c_int64
     lib.dp_effects_workspace_size.restype = ctypes.c_int64
+    lib.dp_shadows_workspace_size.restype = ctypes.c_int64
     lib.dp_gemm_debug_flags.argtypes = [ctypes.c_int]
     lib.dp_gemm_debug_flags.restype = ctypes.c_int
     ver = lib.dp_abi_version()

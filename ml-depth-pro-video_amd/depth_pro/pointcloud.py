@@ -44,6 +44,10 @@ Floor-plan polygons (the rest of that file: `findContours`, `approximate_contour
 `region_outlines`, `simplify_outlines`, `floor_mean_height` and `floor_polygons` on a `floor_plan` result --
 csrc/dp_outline.hip, no OpenCV, no shapely, no host read-back; `floor_polygons_summary` makes the one read-back
 and `export_floorplan_text` writes the reference's `{base}_floorplan.txt`.
+
+Depth shadows in image space (`find_depth_shadows` and the ground fill of `remove_depth_shadows`,
+`OLD_SCRIPTS/mesh_from_depth.py`) live in `depth_pro.shadows` (csrc/dp_shadows.hip): they work on the depth map, ahead
+of `dp_depth_to_points`, which drops the pixels they set to NaN.
 """
 
 from __future__ import annotations

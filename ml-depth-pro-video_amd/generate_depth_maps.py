@@ -40,6 +40,7 @@ import depth_pro  # noqa: E402  (this package's drop-in)
 from depth_pro import distributed as D  # noqa: E402
 from depth_pro import effects as FX  # noqa: E402
 from depth_pro import pointcloud as PC  # noqa: E402
+from depth_pro import shadows as SH  # noqa: E402
 
 
 def colorize_depth(depth, min_depth=None, max_depth=None, cmap="turbo"):
@@ -65,7 +66,7 @@ def raw_depth_u16(depth_np: np.ndarray) -> np.ndarray:
 
 
 def _png_parts(arr: np.ndarray, level: int = 1) -> list:
-    """The PNG file of an 8-bit RGB (H, W, 3) or 16-bit greyscale (H, W) image as a list of byte
+    """The PNG file of an 8-bit RGB (H, W, 3), 16-bit or 8-bit greyscale (H, W) image as a list of byte
     pieces: filter type 0 on every row and one zlib stream (level 1) -- the same pixels as any PNG
     writer (the reference's cv2.imwrite included), ~3x faster than PIL's adaptive filtering.
     zlib (compress, crc32) runs without the GIL and nothing here copies the image or the
@@ -77,6 +78,8 @@ def _png_parts(arr: np.ndarray, level: int = 1) -> list:
         depth, ctype, rows = 16, 0, arr.astype(">u2").view(np.uint8).reshape(arr.shape[0], -1)
     elif arr.dtype == np.uint8 and arr.ndim == 3 and arr.shape[2] == 3:
         depth, ctype, rows = 8, 2, arr.reshape(arr.shape[0], -1)
+    elif arr.dtype == np.uint8 and arr.ndim == 2:
+        depth, ctype, rows = 8, 0, arr
     else:
         raise ValueError(f"_png_bytes: unsupported image {arr.dtype} {arr.shape}")
     h, w = arr.shape[0], arr.shape[1]
@@ -248,6 +251,8 @@ floorplan_json_name = partial(frame_file, suffix="_floorplan.json")
 boundary_name = partial(frame_file, suffix="_boundary.json")            # --boundary_dir: the score against `{base}.npy` there
 anaglyph_name = partial(frame_file, suffix="_anaglyph.png")             # --anaglyph
 parallax_name = partial(frame_file, suffix="_parallax.png")             # --parallax
+shadows_name = partial(frame_file, suffix="_shadows.png")               # --depth_shadows; parameters and counts beside it
+shadows_json_name = partial(frame_file, suffix="_shadows.json")
 
 
 def cloud_name(image_path: str, cleaned: bool = False) -> str:
@@ -289,16 +294,22 @@ def plan_frames(image_paths, output_dir: str, world: int, rank: int, resume: boo
     return [todo[i] for i in D.shard_frames(len(todo), rank, world)]
 
 
+def _stages_on(o: dict) -> set:
+    """The names of the stages that are on for the options `o` (all of them present): asked for, or implied."""
+    on = set()
+    for st in reversed(STAGES):             # a stage stands behind every stage it implies
+        if st.name in on or st.on(o):
+            on |= {st.name, st.implies} - {None}
+    return on
+
+
 def resolve_stages(**options) -> dict:
     """The stages a run has on, from the loop's options (`batch_generate_depth_maps`'s keywords; one left out has
     its default): {stage name: its parameter dict}, in the order of `STAGES`.  A stage is on when its own option is,
     or when a stage that is on implies it; the options of the stages that are on are checked (ValueError), the
     others are not looked at.  Touches no GPU and no file (but `check_boundary_dir`'s isdir)."""
     o = {**_DEFAULTS, **options}
-    on = set()
-    for st in reversed(STAGES):             # a stage stands behind every stage it implies
-        if st.name in on or st.on(o):
-            on |= {st.name, st.implies} - {None}
+    on = _stages_on(o)
     params = {st.name: st.params(o) for st in reversed(STAGES) if st.name in on}
     return {st.name: params[st.name] for st in STAGES if st.name in on}
 
@@ -314,7 +325,8 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                               boundary_dir=None, split_l_shapes=False, simple_mesh=False, mesh_neighbors=6,
                               floor_polygons=False, floor_slices=0, floor_slice_min=0.1, floor_slice_max=2.5,
                               floor_slice_resolution=0.05, floor_slice_min_area=0.1, anaglyph=False,
-                              anaglyph_separation=0.05, parallax=None, parallax_amplitude=0.05, parallax_period=150):
+                              anaglyph_separation=0.05, parallax=None, parallax_amplitude=0.05, parallax_period=150,
+                              depth_shadows=False, shadow_threshold=0.2, shadow_min_region=100, drop_depth_shadows=False):
     """Directory loop (reference :153-206), pipelined decode -> GPU -> encode, frame-sharded across ranks.
 
     Every rank writes its own frames' files; each frame has exactly one owner.  resume=True skips
@@ -388,6 +400,13 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
     directory of parallax_period copies of one still reproduces the reference's video frame by frame, a real video
     gets the camera motion laid over it; the phase does not depend on how the frames are dealt to the ranks.
     Both report, in one line per frame, the pixels written black for want of a finite depth when there are any.
+    depth_shadows=True writes `{base}_shadows.png` (8-bit grey, 255 = shadow) and `{base}_shadows.json` (parameters, counts
+    by name, gmax, nonfinite): the reference's find_depth_shadows (OLD_SCRIPTS/mesh_from_depth.py :1110-1170) of the depth
+    still on the device (`depth_pro.shadows.find_depth_shadows` with shadow_threshold as its threshold_factor and
+    shadow_min_region as its min_region_size), queued ahead of the cloud.
+    drop_depth_shadows=True (implies depth_shadows; needs the cloud: pointcloud or a stage that implies it, else
+    ValueError) back-projects the depth with the shadow pixels set to NaN, so the cloud and every later stage are without
+    them.  This use of the mask is this project's own: the reference fills the shadow pixels and never drops them.
     """
     params = resolve_stages(**{k: v for k, v in locals().items() if k in _DEFAULTS}, output_dir=output_dir)
     on = [st for st in STAGES if st.name in params]
@@ -600,7 +619,7 @@ def _ground_plane(ground: dict, xyz, count, image_path):
 def _backproject(frame: dict, p=None) -> None:
     """Queue the frame's point cloud on the GPU (depth_to_3d, img_to_normalized_pointcloud.py:819-856) on the
     current stream, without a host synchronisation: points, colours and the point count, all on the device."""
-    depth, image = frame["depth"], frame["image"]
+    depth, image = frame.get("cloud_depth", frame["depth"]), frame["image"]     # --drop_depth_shadows: shadows are NaN
     h, w = depth.shape
     rgb = image.to(depth.device, non_blocking=True) if torch.is_tensor(image) else \
         torch.from_numpy(np.ascontiguousarray(image)).to(depth.device, non_blocking=True)
@@ -925,6 +944,28 @@ def _write_parallax(base: str, params: dict, out: dict) -> None:
     _write_view(base + "_parallax.png", out["parallax"])
 
 
+def _queue_shadows(frame: dict, p: dict) -> dict:
+    """The depth-shadow mask of the frame (--depth_shadows), ahead of the cloud: gradient, edges, region filter; with
+    --drop_depth_shadows the cloud stage then back-projects the depth with the shadow pixels set to NaN."""
+    res = SH.find_depth_shadows(frame["depth"], p["threshold_factor"], p["min_region_size"], drop=p["drop"])
+    if p["drop"]:
+        frame["cloud_depth"] = res["depth"]
+    return {"mask": _pinned(res["mask"]), "stats": _pinned(res["stats"])}
+
+
+def _write_shadows(base: str, params: dict, out: dict) -> None:
+    """Writer-thread side (after the frame's event): `{base}_shadows.png` (8-bit grey, 255 = shadow) and `{base}_shadows.json`."""
+    s, p = out["shadows"], params["shadows"]
+    mask = s["mask"].numpy()
+    _write_png(base + "_shadows.png", mask * np.uint8(255))
+    stats = SH.stats_dict(s["stats"].numpy())
+    with open(base + "_shadows.json", "w") as f:
+        json.dump({"parameters": {"threshold_factor": p["threshold_factor"], "min_region_size": p["min_region_size"],
+                                  "drop": p["drop"]},
+                   "H": int(mask.shape[0]), "W": int(mask.shape[1]), "counts": {k: v for k, v in stats.items() if k != "gmax"},
+                   "gmax": stats["gmax"], "nonfinite": stats["nonfinite"]}, f, indent=1)
+
+
 # ---- each stage's parameter dict from the loop's options `o`, checked first ----
 
 def _ground_params(o: dict) -> dict:
@@ -1002,6 +1043,21 @@ def _parallax_params(o: dict) -> dict:
     return {"motion": o["parallax"], "amplitude": float(o["parallax_amplitude"]), "period": int(o["parallax_period"])}
 
 
+def check_shadows(threshold, min_region) -> None:
+    if not np.isfinite(float(threshold)):
+        raise ValueError(f"--shadow_threshold must be finite (got {threshold})")
+    if int(min_region) < 0:
+        raise ValueError(f"--shadow_min_region must be >= 0 (got {min_region})")
+
+
+def _shadows_params(o: dict) -> dict:
+    check_shadows(o["shadow_threshold"], o["shadow_min_region"])
+    if o["drop_depth_shadows"] and "cloud" not in _stages_on(o):
+        raise ValueError("--drop_depth_shadows requires --pointcloud (there is no cloud to drop the shadow pixels from)")
+    return {"threshold_factor": float(o["shadow_threshold"]), "min_region_size": int(o["shadow_min_region"]),
+            "drop": bool(o["drop_depth_shadows"])}
+
+
 class Stage(NamedTuple):
     """One stage of the frame loop, described once."""
     name: str
@@ -1016,6 +1072,8 @@ class Stage(NamedTuple):
 
 # in the order they are queued on a frame's stream; a stage stands behind the one it implies
 STAGES = (
+    Stage("shadows", None, lambda o: bool(o["depth_shadows"] or o["drop_depth_shadows"]), _shadows_params,
+          ("_shadows.png", "_shadows.json"), _queue_shadows, _write_shadows),
     Stage("cloud", None, lambda o: o["pointcloud"], lambda o: {}, (), _backproject, _write_cloud),
     Stage("ground", "cloud", lambda o: o["normalize_ground"], _ground_params, (), _queue_ground, None, _end_ground),
     Stage("clean", "ground", lambda o: o["clean_pointcloud"], _clean_params, ("_clean.ply",), _queue_clean, None),
@@ -1098,7 +1156,7 @@ def main():
                         help="Voxel edge of --mesh_points in metres (default 0.05); normals use radius 2 * voxel_size")
     parser.add_argument("--normals_max_nn", type=int, default=30,
                         help=f"Neighbours at the most per normal (1..{PC.MAX_NN}, default 30)")
-    # the two options below (and --floor_polygons, --floor_slices, --anaglyph, --parallax and their options) are passed on only when given: a run without them passes the keywords it always passed
+    # the two options below (and --floor_polygons, --floor_slices, --anaglyph, --parallax, --depth_shadows and their options) are passed on only when given: a run without them passes the keywords it always passed
     parser.add_argument("--simple_mesh", action="store_true", default=argparse.SUPPRESS,
                         help="Mesh the voxels of --mesh_points (which it implies) as the reference's --mesh_method simple "
                              "does: nearest neighbours, a fan of triangles, clean-up; {frame}_mesh.ply and {frame}_mesh.json")
@@ -1138,6 +1196,16 @@ def main():
                         help="Amplitude of the camera motion of --parallax (default 0.05; 0.01-0.2 recommended)")
     parser.add_argument("--parallax_period", type=int, default=argparse.SUPPRESS,
                         help="Frames per cycle of --parallax (default 150: 5 s at 30 frames/s)")
+    parser.add_argument("--depth_shadows", action="store_true", default=argparse.SUPPRESS,
+                        help="Write {frame}_shadows.png (8-bit, 255 = shadow) and {frame}_shadows.json: the depth-discontinuity "
+                             "shadow mask of the frame's depth (the reference's find_depth_shadows)")
+    parser.add_argument("--shadow_threshold", type=float, default=argparse.SUPPRESS,
+                        help="Normalised gradient above which a pixel is an edge for --depth_shadows (default 0.2)")
+    parser.add_argument("--shadow_min_region", type=int, default=argparse.SUPPRESS,
+                        help="Free regions of fewer pixels than this are shadow for --depth_shadows (default 100)")
+    parser.add_argument("--drop_depth_shadows", action="store_true", default=argparse.SUPPRESS,
+                        help="Leave the shadow pixels out of the point cloud (implies --depth_shadows, requires --pointcloud); "
+                             "the reference fills them instead, dropping them is this project's own")
     parser.add_argument("--boundary_dir", type=str, default=None,
                         help="Score each frame against DIR/{frame}.npy with the Depth Pro boundary metric (float32: a depth, "
                              "SI_boundary_F1; bool / uint8: a mask, SI_boundary_Recall); writes {frame}_boundary.json")
@@ -1148,7 +1216,8 @@ def main():
                              "with --floor_plan: and {frame}_floorplan.png / .json; with --floor_polygons: and {frame}_floorplan.txt / "
                              "_floorplan_polygons.json; with --floor_slices: and {frame}_floorslices.txt / .json; with "
                              "--boundary_dir, for a frame with a target: and {frame}_boundary.json; with --anaglyph: and "
-                             "{frame}_anaglyph.png; with --parallax: and {frame}_parallax.png) already exists in --output_dir")
+                             "{frame}_anaglyph.png; with --parallax: and {frame}_parallax.png; with --depth_shadows: and {frame}_shadows.png / "
+                             ".json) already exists in --output_dir")
     parser.add_argument("--colormap", type=str, default="turbo",
                         choices=["turbo", "viridis", "plasma", "inferno", "magma", "cividis", "jet"],
                         help="Colormap for depth visualization")

@@ -53,6 +53,9 @@ def main():
     ap.add_argument("--anaglyph", action="store_true", help="write the red-cyan anaglyphs (--anaglyph of the loop)")
     ap.add_argument("--parallax", default=None, choices=["circle", "zoom", "swing"],
                     help="write the parallax frames (--parallax of the loop)")
+    ap.add_argument("--depth-shadows", action="store_true", help="write the depth-shadow masks (--depth_shadows of the loop)")
+    ap.add_argument("--drop-depth-shadows", action="store_true",
+                    help="leave the shadow pixels out of the clouds (--drop_depth_shadows of the loop; needs a cloud)")
     ap.add_argument("--raw", action="store_true")
     ap.add_argument("--workers", type=int, default=None,
                     help="decode and encode threads each (default: the loop's own defaults)")
@@ -137,7 +140,8 @@ def main():
     # the stage flags go to the loop as they are: it implies the rest (G.resolve_stages)
     flags = {k: getattr(args, k) for k in ("pointcloud", "normalize_ground", "clean_pointcloud", "cluster_pointcloud",
                                            "fit_shapes", "split_l_shapes", "mesh_points", "floor_plan")}
-    flags.update({k: getattr(args, k) for k in ("anaglyph", "parallax") if getattr(args, k)})      # only when asked for
+    flags.update({k: getattr(args, k) for k in ("anaglyph", "parallax", "depth_shadows", "drop_depth_shadows")
+                  if getattr(args, k)})                                                            # only when asked for
     stages = list(G.resolve_stages(**flags))
     kw = dict(colored=not args.raw, model=model, **flags)
     if args.workers:

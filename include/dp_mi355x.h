@@ -1760,6 +1760,56 @@ int dp_depth_shadows(const float* depth, int32_t h, int32_t w, double threshold_
 int dp_fill_ground_shadows(const float* depth, const uint8_t* shadow, int32_t h, int32_t w, const double* plane,
                            double ground_rows, float* depth_out, int64_t* filled_out, dp_stream_t stream);
 
+/*
+ * ---- Point-cloud views (ABI 20, additive; csrc/dp_render.hip) -------------------------------------------------
+ * Pictures of a cloud on the device: z-buffered square splats from up to DP_RENDER_MAX_VIEWS perspective cameras (the
+ * reference's Open3D presets front / top / side / isometric of render_point_cloud_to_image and visualize_pointcloud)
+ * and the orthographic top-down `plan` of pointcloud_pipeline.py's in_memory_pointcloud_visualization.  Everything runs
+ * on the caller's stream as separate launches, with no synchronisation and no read-back.  The rule is DESIGN.md
+ * section 22, restated in tests/render_numpy.py; all arithmetic is fp64 in the order written there, without FMA.
+ *   points     fp64 [n][3]; the first *count rows are live (count: device int32, null = n); a row with a non-finite
+ *              coordinate is counted and takes no part          colors   uint8 [n][3] or null (128, 128, 128)
+ *   views      HOST fp64 [n_views][7] = front (3), up (3), zoom; read during the call
+ *   plan       0: no plan view; 1: the plan of every finite row; 2: of the rows with y >= min_height.  The plan is the
+ *              last view of the call.
+ *   size       the splat's side in pixels, odd, 1 .. DP_RENDER_MAX_SIZE
+ *   background HOST uint8 [6]: the perspective views' background, then the plan's
+ *   tan_half_fov  tan(30 degrees) for the reference's 60 degree field of view, as the caller's libm gives it
+ *   image_out  uint8 [n_views + (plan != 0)][H][W][3]; with sheet != 0 (exactly 4 views, no plan) uint8 [2H][2W][3]
+ *              with view 0 top-left, 1 top-right, 2 bottom-left, 3 bottom-right
+ *   cameras_out  device fp64 [views][DP_RENDER_CAMERA_DOUBLES]: kind (0 perspective, 1 plan), degenerate, then for a
+ *              perspective view eye [2..4], s [5..7], u [8..10], F [11..13], near, far, dist, extent, centre [18..20],
+ *              t * (W / H), t; for the plan centre x', centre z, scale, y_top, min_height (NaN: none), (W - 1) / 2,
+ *              (H - 1) / 2.  A degenerate view (no finite row, or an extent that is not > 0; the plan: no shown row) is
+ *              all background.
+ *   stats_out  device fp64 [DP_RENDER_STATS]: LIVE, NONFINITE, DEGENERATE, ERROR (1 when NONFINITE > 0), then per view
+ *              at DP_RENDER_STAT_VIEWS + 4 v: drawn, clipped (the plan: below min_height), outside, covered pixels
+ *   workspace  >= dp_render_workspace_size(W, H, size, views) bytes (0 for arguments it refuses), 8-byte aligned, owned
+ *              by the call until the stream has passed it; dp_render_cameras uses the first 256 bytes only
+ * DP_ERR_ARG before any launch: a null pointer (colors and count may be null; views when n_views = 0), n < 0, W or
+ * H < 1, W * H >= 2^31, size even or outside 1 .. 15, n_views > 4 or no view at all, a front, up or zoom that is zero
+ * or not finite, a zoom < 0, up parallel to front, a min_height (plan = 2) or tan_half_fov that is not finite, a sheet
+ * without exactly four views, a workspace that is null, short or misaligned.
+ */
+#define DP_RENDER_MAX_VIEWS       4
+#define DP_RENDER_MAX_SIZE        15
+#define DP_RENDER_CAMERA_DOUBLES  24
+#define DP_RENDER_STATS           24
+#define DP_RENDER_STAT_LIVE       0
+#define DP_RENDER_STAT_NONFINITE  1
+#define DP_RENDER_STAT_DEGENERATE 2
+#define DP_RENDER_STAT_ERROR      3
+#define DP_RENDER_STAT_VIEWS      4
+int64_t dp_render_workspace_size(int32_t W, int32_t H, int32_t size, int32_t n_views);
+int dp_render_cameras(const double* points, const int32_t* count, int32_t n, const double* views, int32_t n_views,
+                      int32_t plan, double min_height, int32_t W, int32_t H, double tan_half_fov, double* cameras_out,
+                      double* stats_out, void* workspace, int64_t workspace_bytes, dp_stream_t stream);
+int dp_render_points(const double* points, const uint8_t* colors, const int32_t* count, int32_t n, const double* views,
+                     int32_t n_views, int32_t plan, double min_height, int32_t W, int32_t H, int32_t size,
+                     const uint8_t* background, double tan_half_fov, int32_t sheet, uint8_t* image_out,
+                     double* cameras_out, double* stats_out, void* workspace, int64_t workspace_bytes,
+                     dp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

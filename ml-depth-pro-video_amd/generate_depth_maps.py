@@ -41,6 +41,7 @@ from depth_pro import distributed as D  # noqa: E402
 from depth_pro import effects as FX  # noqa: E402
 from depth_pro import pointcloud as PC  # noqa: E402
 from depth_pro import shadows as SH  # noqa: E402
+from depth_pro import render as RV  # noqa: E402
 
 
 def colorize_depth(depth, min_depth=None, max_depth=None, cmap="turbo"):
@@ -253,6 +254,8 @@ anaglyph_name = partial(frame_file, suffix="_anaglyph.png")             # --anag
 parallax_name = partial(frame_file, suffix="_parallax.png")             # --parallax
 shadows_name = partial(frame_file, suffix="_shadows.png")               # --depth_shadows; parameters and counts beside it
 shadows_json_name = partial(frame_file, suffix="_shadows.json")
+view_name = partial(frame_file, suffix="_view.png")                     # --render_view; cameras and counts beside it
+view_json_name = partial(frame_file, suffix="_view.json")
 
 
 def cloud_name(image_path: str, cleaned: bool = False) -> str:
@@ -326,7 +329,8 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                               floor_polygons=False, floor_slices=0, floor_slice_min=0.1, floor_slice_max=2.5,
                               floor_slice_resolution=0.05, floor_slice_min_area=0.1, anaglyph=False,
                               anaglyph_separation=0.05, parallax=None, parallax_amplitude=0.05, parallax_period=150,
-                              depth_shadows=False, shadow_threshold=0.2, shadow_min_region=100, drop_depth_shadows=False):
+                              depth_shadows=False, shadow_threshold=0.2, shadow_min_region=100, drop_depth_shadows=False,
+                              render_view=None, render_size="1280x720", render_point_size=7, render_min_height=None):
     """Directory loop (reference :153-206), pipelined decode -> GPU -> encode, frame-sharded across ranks.
 
     Every rank writes its own frames' files; each frame has exactly one owner.  resume=True skips
@@ -407,6 +411,11 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
     drop_depth_shadows=True (implies depth_shadows; needs the cloud: pointcloud or a stage that implies it, else
     ValueError) back-projects the depth with the shadow pixels set to NaN, so the cloud and every later stage are without
     them.  This use of the mask is this project's own: the reference fills the shadow pixels and never drops them.
+    render_view="front" | "top" | "side" | "isometric" | "multi" | "plan" (implies pointcloud) writes `{base}_view.png`, a
+    picture of the frame's latest cloud (the cleaned one with clean_pointcloud, the levelled one with normalize_ground,
+    else the raw one) made on the device (`depth_pro.render.render_views`: the reference's view presets, `multi` their
+    2 x 2 sheet, `plan` the main pipeline's top-down picture, render_min_height its height threshold) at render_size
+    ("WxH") with splats of render_point_size pixels, and `{base}_view.json` (the cameras and the counts).
     """
     params = resolve_stages(**{k: v for k, v in locals().items() if k in _DEFAULTS}, output_dir=output_dir)
     on = [st for st in STAGES if st.name in params]
@@ -966,6 +975,27 @@ def _write_shadows(base: str, params: dict, out: dict) -> None:
                    "gmax": stats["gmax"], "nonfinite": stats["nonfinite"]}, f, indent=1)
 
 
+def _queue_views(frame: dict, p: dict) -> dict:
+    """The picture of the frame's cloud as the stages so far have left it (--render_view): bounds, cameras, one pass over
+    the rows, the splats; then the pinned host copies."""
+    res = RV.render_views(frame["xyz"], frame["cols"], views=p["views"], size=p["size"], point_size=p["point_size"],
+                          count=frame["count"], sheet=p["sheet"], min_height=p["min_height"])
+    return {k: _pinned(v) for k, v in res.items()}
+
+
+def _write_views(base: str, params: dict, out: dict) -> None:
+    """Writer-thread side (after the frame's event): `{base}_view.png` (RGB) and `{base}_view.json`."""
+    r, p = out["views"], params["views"]
+    image = r["image"].numpy()
+    _write_png(base + "_view.png", image if p["sheet"] else image[0])
+    cams = r["cameras"].numpy()
+    with open(base + "_view.json", "w") as f:
+        json.dump({"parameters": {"view": p["view"], "size": list(p["size"]), "point_size": p["point_size"],
+                                  "min_height": p["min_height"]},
+                   "views": list(p["views"]), "cameras": [[None if c != c else float(c) for c in cam] for cam in cams],
+                   "counts": RV.stats_dict(r["stats"].numpy(), len(cams))}, f, indent=1)
+
+
 # ---- each stage's parameter dict from the loop's options `o`, checked first ----
 
 def _ground_params(o: dict) -> dict:
@@ -1058,6 +1088,34 @@ def _shadows_params(o: dict) -> dict:
             "drop": bool(o["drop_depth_shadows"])}
 
 
+RENDER_VIEWS = tuple(RV.VIEW_PRESETS) + ("multi", RV.PLAN)
+
+
+def check_render(view, size, point_size, min_height) -> Tuple[int, int]:
+    if view not in RENDER_VIEWS:
+        raise ValueError(f"--render_view must be one of {', '.join(RENDER_VIEWS)} (got {view})")
+    try:
+        w, h = (int(v) for v in str(size).lower().split("x"))
+    except ValueError:
+        raise ValueError(f"--render_size must be WxH (got {size})") from None
+    if w < 1 or h < 1 or w * h >= 2 ** 31:
+        raise ValueError(f"--render_size: W and H must be >= 1 and W * H < 2^31 (got {size})")
+    if not (1 <= int(point_size) <= 15 and int(point_size) % 2 == 1):
+        raise ValueError(f"--render_point_size must be odd and in [1, 15] (got {point_size})")
+    if min_height is not None and not np.isfinite(float(min_height)):
+        raise ValueError(f"--render_min_height must be finite (got {min_height})")
+    return w, h
+
+
+def _views_params(o: dict) -> dict:
+    size = check_render(o["render_view"], o["render_size"], o["render_point_size"], o["render_min_height"])
+    view = o["render_view"]
+    plan = view == RV.PLAN
+    return {"view": view, "views": RV.SHEET if view == "multi" else (view,), "sheet": view == "multi", "size": size,
+            "point_size": int(o["render_point_size"]),
+            "min_height": float(o["render_min_height"]) if plan and o["render_min_height"] is not None else None}
+
+
 class Stage(NamedTuple):
     """One stage of the frame loop, described once."""
     name: str
@@ -1077,6 +1135,8 @@ STAGES = (
     Stage("cloud", None, lambda o: o["pointcloud"], lambda o: {}, (), _backproject, _write_cloud),
     Stage("ground", "cloud", lambda o: o["normalize_ground"], _ground_params, (), _queue_ground, None, _end_ground),
     Stage("clean", "ground", lambda o: o["clean_pointcloud"], _clean_params, ("_clean.ply",), _queue_clean, None),
+    Stage("views", "cloud", lambda o: o["render_view"] is not None, _views_params, ("_view.png", "_view.json"),
+          _queue_views, _write_views),
     Stage("cluster", "clean", lambda o: o["cluster_pointcloud"], _cluster_params, ("_clusters.json",),
           _queue_cluster, _write_clusters),
     Stage("shapes", "cluster", lambda o: o["fit_shapes"] or o["split_l_shapes"], _shapes_params, ("_shapes.json",),
@@ -1156,7 +1216,7 @@ def main():
                         help="Voxel edge of --mesh_points in metres (default 0.05); normals use radius 2 * voxel_size")
     parser.add_argument("--normals_max_nn", type=int, default=30,
                         help=f"Neighbours at the most per normal (1..{PC.MAX_NN}, default 30)")
-    # the two options below (and --floor_polygons, --floor_slices, --anaglyph, --parallax, --depth_shadows and their options) are passed on only when given: a run without them passes the keywords it always passed
+    # the two options below (and --floor_polygons, --floor_slices, --anaglyph, --parallax, --depth_shadows, --render_view and their options) are passed on only when given: a run without them passes the keywords it always passed
     parser.add_argument("--simple_mesh", action="store_true", default=argparse.SUPPRESS,
                         help="Mesh the voxels of --mesh_points (which it implies) as the reference's --mesh_method simple "
                              "does: nearest neighbours, a fan of triangles, clean-up; {frame}_mesh.ply and {frame}_mesh.json")
@@ -1206,6 +1266,16 @@ def main():
     parser.add_argument("--drop_depth_shadows", action="store_true", default=argparse.SUPPRESS,
                         help="Leave the shadow pixels out of the point cloud (implies --depth_shadows, requires --pointcloud); "
                              "the reference fills them instead, dropping them is this project's own")
+    parser.add_argument("--render_view", type=str, choices=list(RENDER_VIEWS), default=argparse.SUPPRESS,
+                        help="Write {frame}_view.png, a picture of the frame's latest point cloud made on the GPU (implies "
+                             "--pointcloud): one of the reference's view presets, multi (their 2 x 2 sheet) or plan (top-down), "
+                             "and {frame}_view.json (the cameras and the counts)")
+    parser.add_argument("--render_size", type=str, default=argparse.SUPPRESS, metavar="WxH",
+                        help="Size of the picture of --render_view (default 1280x720; each quadrant of multi has this size)")
+    parser.add_argument("--render_point_size", type=int, default=argparse.SUPPRESS,
+                        help="Side of a point's square in pixels for --render_view, odd, 1..15 (default 7)")
+    parser.add_argument("--render_min_height", type=float, default=argparse.SUPPRESS,
+                        help="Show only the points with y >= this height in --render_view plan (default: all)")
     parser.add_argument("--boundary_dir", type=str, default=None,
                         help="Score each frame against DIR/{frame}.npy with the Depth Pro boundary metric (float32: a depth, "
                              "SI_boundary_F1; bool / uint8: a mask, SI_boundary_Recall); writes {frame}_boundary.json")
@@ -1217,7 +1287,7 @@ def main():
                              "_floorplan_polygons.json; with --floor_slices: and {frame}_floorslices.txt / .json; with "
                              "--boundary_dir, for a frame with a target: and {frame}_boundary.json; with --anaglyph: and "
                              "{frame}_anaglyph.png; with --parallax: and {frame}_parallax.png; with --depth_shadows: and {frame}_shadows.png / "
-                             ".json) already exists in --output_dir")
+                             ".json; with --render_view: and {frame}_view.png / .json) already exists in --output_dir")
     parser.add_argument("--colormap", type=str, default="turbo",
                         choices=["turbo", "viridis", "plasma", "inferno", "magma", "cividis", "jet"],
                         help="Colormap for depth visualization")

@@ -56,6 +56,8 @@ def main():
     ap.add_argument("--depth-shadows", action="store_true", help="write the depth-shadow masks (--depth_shadows of the loop)")
     ap.add_argument("--drop-depth-shadows", action="store_true",
                     help="leave the shadow pixels out of the clouds (--drop_depth_shadows of the loop; needs a cloud)")
+    ap.add_argument("--render-view", default=None, choices=["front", "top", "side", "isometric", "multi", "plan"],
+                    help="write a picture of every frame's latest cloud (--render_view of the loop; implies --pointcloud)")
     ap.add_argument("--raw", action="store_true")
     ap.add_argument("--workers", type=int, default=None,
                     help="decode and encode threads each (default: the loop's own defaults)")
@@ -140,7 +142,7 @@ def main():
     # the stage flags go to the loop as they are: it implies the rest (G.resolve_stages)
     flags = {k: getattr(args, k) for k in ("pointcloud", "normalize_ground", "clean_pointcloud", "cluster_pointcloud",
                                            "fit_shapes", "split_l_shapes", "mesh_points", "floor_plan")}
-    flags.update({k: getattr(args, k) for k in ("anaglyph", "parallax", "depth_shadows", "drop_depth_shadows")
+    flags.update({k: getattr(args, k) for k in ("anaglyph", "parallax", "depth_shadows", "drop_depth_shadows", "render_view")
                   if getattr(args, k)})                                                            # only when asked for
     stages = list(G.resolve_stages(**flags))
     kw = dict(colored=not args.raw, model=model, **flags)

@@ -3,8 +3,10 @@
 // cleaned_pointcloud_to_floorplan.py in front of the contour tracing.  The specification is in dp_mi355x.h.
 // fp64 with no FMA contraction where coordinates are involved.  The grid's size is only known on the device
 // (dims), so every kernel is launched for the caller's capacity and strides over the cells that exist.
+// The extent rule, the raster's wave join, the packed morphology and the linking of the regions are shared with
+// the height slices and live in dp_grid2.h, where this grid is the stack of one slice.
 #include "dp_common.h"
-#include "dp_points.h"
+#include "dp_grid2.h"
 
 #pragma clang fp contract(off)
 
@@ -75,11 +77,7 @@ __global__ void grid_setup_kernel(Hdr* h, double res, double padding, int max_ce
   if (!h->ctr[C_PART]) {
     err = 1;
   } else {
-    ox = unkey(h->mm[0]) - padding;
-    oz = unkey(h->mm[2]) - padding;
-    W = axis_cells(ox, unkey(h->mm[1]) + padding, res);
-    H = axis_cells(oz, unkey(h->mm[3]) + padding, res);
-    if (W < 0 || H < 0 || (long long)W * H > max_cells) { err = 2; H = 0; W = 0; }
+    err = grid_extent(h->mm, padding, res, max_cells, ox, oz, H, W);
   }
   h->par[0] = ox; h->par[1] = oz; h->par[2] = res;
   h->dim[0] = dims[0] = H;
@@ -96,9 +94,7 @@ __global__ void __launch_bounds__(256) grid_clear_kernel(const Hdr* h, u64* __re
   }
 }
 
-// One row per lane.  The rows of a wave mostly fall into a few cells (the cloud is in image order), so the
-// wave first joins its rows cell by cell: the lanes of the first pending lane's cell add their number and
-// the largest of their keys with one atomic each, until no lane is pending.  The loop is wave-uniform.
+// One row per lane; the wave joins the rows of one cell before it touches the cell (dp_grid2.h).
 __global__ void __launch_bounds__(256) raster_kernel(const double* __restrict__ pts, const int32_t* n_dev, int n_max, double thr,
                                                      Hdr* h, u64* __restrict__ keys, uint32_t* __restrict__ density) {
   const int n = live_n(n_dev, n_max), lane = threadIdx.x & 63;
@@ -125,24 +121,7 @@ __global__ void __launch_bounds__(256) raster_kernel(const double* __restrict__ 
         }
       }
     }
-    u64 todo = __ballot(valid);
-    while (todo) {
-      const int leader = __ffsll((long long)todo) - 1;
-      const int lc = __shfl(cell, leader);
-      const bool mine = valid && cell == lc;
-      const u64 m = __ballot(mine);
-      u64 k = mine ? key : 0;
-      #pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const u64 t = __shfl_xor(k, o);
-        k = t > k ? t : k;
-      }
-      if (lane == leader) {
-        atomicAdd(&density[lc], (uint32_t)__popcll(m));
-        atomicMax(&keys[lc], k);
-      }
-      todo &= ~m;
-    }
+    wave_join_cells(valid, cell, key, density, keys);
   }
   #pragma unroll
   for (int o = 32; o > 0; o >>= 1) dropped += __shfl_xor(dropped, o);
@@ -181,123 +160,15 @@ __global__ void grid_stats_kernel(const Hdr* h, double* st) {
   st[7] = (double)h->ctr[C_ERR];
 }
 
-// ---- morphology -----------------------------------------------------------------------------------
-// A row is packed 64 cells to a word, bit i of word j = cell 64 j + i; the bits past W in a row's last
-// word are kept 0.  One wave packs one word: the ballot of "my cell is set".
-
-__global__ void __launch_bounds__(256) pack_kernel(const uint8_t* __restrict__ grid, const int32_t* dims, int max_cells,
-                                                   u64* __restrict__ bits) {
-  int H, W;
-  grid_dims(dims, max_cells, H, W);
-  const int WW = (W + 63) >> 6, lane = threadIdx.x & 63;
-  const long long words = (long long)H * WW;
-  for (long long t = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); t < words; t += (long long)gridDim.x * 4) {
-    const int r = (int)(t / WW), gx = (int)(t % WW) * 64 + lane;
-    const u64 w = __ballot(gx < W && grid[(long long)r * W + gx] != 0);
-    if (lane == 0) bits[t] = w;
-  }
-}
-
-__global__ void __launch_bounds__(256) unpack_kernel(const u64* __restrict__ bits, const int32_t* dims, int max_cells,
-                                                     uint8_t* __restrict__ grid) {
-  int H, W;
-  grid_dims(dims, max_cells, H, W);
-  const int WW = (W + 63) >> 6;
-  const long long cells = (long long)H * W;
-  for (long long c = (long long)blockIdx.x * 256 + threadIdx.x; c < cells; c += (long long)gridDim.x * 256) {
-    const int r = (int)(c / W), gx = (int)(c % W);
-    grid[c] = (uint8_t)((bits[(long long)r * WW + (gx >> 6)] >> (gx & 63)) & 1);
-  }
-}
-
-// Horizontal pass of a (2 rad + 1)-wide row of ones, one thread per word: shifts of the word and its two
-// neighbours, ORed (dilation: cells outside the grid read 0) or ANDed (erosion: they read 1).
-__global__ void __launch_bounds__(256) morph_h_kernel(const u64* __restrict__ src, u64* __restrict__ dst, const int32_t* dims,
-                                                      int max_cells, int rad, int erode) {
-  int H, W;
-  grid_dims(dims, max_cells, H, W);
-  const int WW = (W + 63) >> 6;
-  const long long words = (long long)H * WW;
-  const u64 fill = erode ? ~0ull : 0ull, tail = tail_mask(W);
-  for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < words; t += (long long)gridDim.x * 256) {
-    const int j = (int)(t % WW);
-    u64 C = src[t];
-    if (j == WW - 1) C = (C & tail) | (fill & ~tail);
-    const u64 L = j > 0 ? src[t - 1] : fill;
-    u64 R = fill;
-    if (j + 1 < WW) {
-      R = src[t + 1];
-      if (j + 1 == WW - 1) R = (R & tail) | (fill & ~tail);
-    }
-    u64 acc = C;
-    for (int s = 1; s <= rad; ++s) {
-      const u64 a = (C >> s) | (R << (64 - s)), b = (C << s) | (L >> (64 - s));
-      acc = erode ? (acc & a & b) : (acc | a | b);
-    }
-    dst[t] = j == WW - 1 ? (acc & tail) : acc;
-  }
-}
-
-// Vertical pass: OR / AND over the 2 rad + 1 row words; a row outside the grid is the neutral element.
-__global__ void __launch_bounds__(256) morph_v_kernel(const u64* __restrict__ src, u64* __restrict__ dst, const int32_t* dims,
-                                                      int max_cells, int rad, int erode) {
-  int H, W;
-  grid_dims(dims, max_cells, H, W);
-  const int WW = (W + 63) >> 6;
-  const long long words = (long long)H * WW;
-  for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < words; t += (long long)gridDim.x * 256) {
-    const int r = (int)(t / WW);
-    u64 acc = src[t];
-    for (int d = -rad; d <= rad; ++d) {
-      const int rr = r + d;
-      if (d == 0 || rr < 0 || rr >= H) continue;
-      const u64 w = src[t + (long long)d * WW];
-      acc = erode ? (acc & w) : (acc | w);
-    }
-    dst[t] = acc;
-  }
-}
-
 // ---- regions --------------------------------------------------------------------------------------
-constexpr uint32_t NO_CELL = ~0u;
-
-__global__ void __launch_bounds__(256) uf_init_kernel(const uint8_t* __restrict__ grid, const int32_t* dims, int max_cells,
-                                                      uint32_t* __restrict__ parent, Hdr* h) {
+// After the last union of dp_grid2.h's linking: every cell points at its root (the region's first cell), and the
+// roots are flagged.  It leaves H * W in the header, where the scan behind it reads its live count.
+__global__ void __launch_bounds__(256) uf_flatten_kernel(Hdr* h, const int32_t* dims, int max_cells, uint32_t* __restrict__ parent,
+                                                         uint8_t* __restrict__ flag) {
   int H, W;
   grid_dims(dims, max_cells, H, W);
   const long long cells = (long long)H * W;
   if (blockIdx.x == 0 && threadIdx.x == 0) h->ncells = (int32_t)cells;
-  for (long long b = (long long)blockIdx.x * 256; b < cells; b += (long long)gridDim.x * 256) {
-    const long long c = b + threadIdx.x;
-    const bool fg = c < cells && grid[c] != 0;
-    if (c < cells) parent[c] = fg ? (uint32_t)c : NO_CELL;
-    wave_count(&h->ctr[C_FG], fg);
-  }
-}
-
-// Every foreground cell is joined to its foreground neighbours to the west, north-west, north and north-east:
-// each 8-connected pair is seen once, from its later cell.
-__global__ void __launch_bounds__(256) uf_link_kernel(const uint8_t* __restrict__ grid, const int32_t* dims, int max_cells,
-                                                      uint32_t* __restrict__ parent) {
-  int H, W;
-  grid_dims(dims, max_cells, H, W);
-  const long long cells = (long long)H * W;
-  for (long long c = (long long)blockIdx.x * 256 + threadIdx.x; c < cells; c += (long long)gridDim.x * 256) {
-    if (!grid[c]) continue;
-    const int r = (int)(c / W), x = (int)(c % W);
-    if (x > 0 && grid[c - 1]) uf_unite(parent, (uint32_t)c, (uint32_t)(c - 1));
-    if (r > 0) {
-      const long long up = c - W;
-      if (x > 0 && grid[up - 1]) uf_unite(parent, (uint32_t)c, (uint32_t)(up - 1));
-      if (grid[up]) uf_unite(parent, (uint32_t)c, (uint32_t)up);
-      if (x + 1 < W && grid[up + 1]) uf_unite(parent, (uint32_t)c, (uint32_t)(up + 1));
-    }
-  }
-}
-
-// after the last union: every cell points at its root (the region's first cell), and the roots are flagged
-__global__ void __launch_bounds__(256) uf_flatten_kernel(const Hdr* h, uint32_t* __restrict__ parent, uint8_t* __restrict__ flag) {
-  const long long cells = h->ncells;
   for (long long c = (long long)blockIdx.x * 256 + threadIdx.x; c < cells; c += (long long)gridDim.x * 256) {
     uint8_t f = 0;
     if (ld(&parent[c]) != NO_CELL) {
@@ -445,8 +316,6 @@ struct Ws {
   uint8_t* flag;
   uint32_t* bc;
 };
-// words of a packed grid: H * ceil(W / 64) <= (H W + 63 H) / 64
-int64_t bit_words_for(int64_t cells) { return cells / 64 + MAX_DIM + 1; }
 int64_t ws_bytes_for(int64_t max_cells, int64_t max_regions) {
   const int64_t n = max_cells < 0 ? 0 : max_cells, k = max_regions < 0 ? 0 : max_regions;
   return al256(sizeof(Hdr)) + al256(8 * n) + 2 * al256(8 * bit_words_for(n)) + al256(4 * n) + al256(n) +
@@ -466,8 +335,6 @@ bool ws_carve(void* ws, int64_t bytes, int64_t max_cells, int64_t max_regions, W
   o->acc = (u64*)p;
   return true;
 }
-bool pos_finite(double v) { return v > 0.0 && v < __builtin_inf(); }
-bool kernel_size_ok(int k) { return k >= 1 && k <= DP_FLOOR_MAX_KERNEL && (k & 1); }
 
 }  // namespace
 
@@ -507,20 +374,9 @@ extern "C" int dp_grid_morphology(const uint8_t* grid, const int32_t* dims, int3
   if (max_cells < 0 || close_iters < 0 || !kernel_size_ok(close_size) || !kernel_size_ok(open_size)) return DP_ERR_SHAPE;
   Ws w;
   if (!ws_carve(workspace, workspace_bytes, max_cells, 0, &w)) return DP_ERR_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t words = bit_words_for(max_cells);
-  const int gw = grid_for(words, GRID_CAP), gc = grid_for(max_cells, GRID_CAP);
-  u64 *a = w.bits_a, *b = w.bits_b;
-  hipLaunchKernelGGL(pack_kernel, dim3(grid_for(64 * words, GRID_CAP)), dim3(256), 0, s, grid, dims, max_cells, a);
-  // one dilation or erosion by a (2 rad + 1)-square: the row pass, then the column pass
-  auto pass = [&](int rad, int erode) {
-    hipLaunchKernelGGL(morph_h_kernel, dim3(gw), dim3(256), 0, s, a, b, dims, max_cells, rad, erode);
-    hipLaunchKernelGGL(morph_v_kernel, dim3(gw), dim3(256), 0, s, b, a, dims, max_cells, rad, erode);
-  };
-  if (close_size > 1)
-    for (int it = 0; it < close_iters; ++it) { pass(close_size / 2, 0); pass(close_size / 2, 1); }
-  if (open_size > 1) { pass(open_size / 2, 1); pass(open_size / 2, 0); }
-  hipLaunchKernelGGL(unpack_kernel, dim3(gc), dim3(256), 0, s, a, dims, max_cells, grid_out);
+  // a closing by one cell changes nothing: no launch for it
+  morphology_launch((hipStream_t)stream, grid, dims, 1, max_cells, nullptr, close_size, close_size > 1 ? close_iters : 0, open_size,
+                    grid_out, w.bits_a, w.bits_b, GRID_CAP);
   DP_CHECK_LAUNCH();
   return 0;
 }
@@ -539,9 +395,9 @@ extern "C" int dp_grid_regions(const uint8_t* grid, const uint32_t* density, con
   const int gc = grid_for(max_cells, GRID_CAP), nb = (int)scan_blocks_for(max_cells);
   uint32_t* parent = (uint32_t*)labels_out;
   hipLaunchKernelGGL(hdr_init_kernel, dim3(1), dim3(1), 0, s, w.h);
-  hipLaunchKernelGGL(uf_init_kernel, dim3(gc), dim3(256), 0, s, grid, dims, max_cells, parent, w.h);
-  hipLaunchKernelGGL(uf_link_kernel, dim3(gc), dim3(256), 0, s, grid, dims, max_cells, parent);
-  hipLaunchKernelGGL(uf_flatten_kernel, dim3(gc), dim3(256), 0, s, w.h, parent, w.flag);
+  hipLaunchKernelGGL(cc_init_kernel, dim3(gc), dim3(256), 0, s, grid, dims, max_cells, parent, &w.h->ctr[C_FG], 0);
+  hipLaunchKernelGGL(cc_link_kernel, dim3(gc), dim3(256), 0, s, grid, dims, max_cells, parent);
+  hipLaunchKernelGGL(uf_flatten_kernel, dim3(gc), dim3(256), 0, s, w.h, dims, max_cells, parent, w.flag);
   if (nb) hipLaunchKernelGGL(scan_count_kernel, dim3(nb), dim3(256), 0, s, w.flag, &w.h->ncells, max_cells, w.bc);
   hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(256), 0, s, w.bc, nb, (uint32_t*)n_regions_dev);   // the same bits
   if (nb) hipLaunchKernelGGL(root_number_kernel, dim3(nb), dim3(256), 0, s, w.flag, w.h, max_cells, w.bc, w.num);

@@ -3,7 +3,8 @@
 // copy of every device and host helper that two or more of them use.  A helper with one user stays in
 // its file.  Everything is in an anonymous namespace, so each translation unit has its own copy of the
 // two kernels below.  The sorted 3-D cell grid of dp_clean.hip, dp_normals.hip and dp_mesh.hip, kernels
-// included, is in dp_grid3.h, which includes this header and which only those three include.
+// included, is in dp_grid3.h, which includes this header and which only those three include; the 2-D grids
+// of dp_floorplan.hip and dp_slices.hip are in dp_grid2.h in the same way.
 // Floating-point contraction: every stage compiles with `#pragma clang fp contract(off)`, and the header
 // sets it as well, so the helpers are built as they were inside the stages wherever the include stands.
 // It is a header for files that want contraction off; cell_of (a subtraction feeding a division) has
@@ -37,20 +38,13 @@ __device__ __forceinline__ uint32_t okey32(float v) {
 }
 __device__ __forceinline__ float unkey32(uint32_t k) { return __uint_as_float((k >> 31) ? (k & 0x7fffffffu) : ~k); }
 
-// ---- floor-plan grids (dp_floorplan.hip, dp_outline.hip, dp_slices.hip) ----------------------------
+// ---- floor-plan grids (dp_floorplan.hip and dp_slices.hip through dp_grid2.h, dp_outline.hip) -------
 // H, W as every stage behind the raster reads them: anything outside [0, DP_FLOOR_MAX_DIM] or beyond the
 // capacity is no grid
 __device__ __forceinline__ void grid_dims(const int32_t* dims, int max_cells, int& H, int& W) {
   H = dims[0]; W = dims[1];
   if (H < 0 || W < 0 || H > DP_FLOOR_MAX_DIM || W > DP_FLOOR_MAX_DIM || (long long)H * W > max_cells) { H = 0; W = 0; }
 }
-// cells along one axis: (int)ceil(((max + padding) - min) / resolution), or -1 for more than DP_FLOOR_MAX_DIM (NaN included)
-__device__ __forceinline__ int axis_cells(double mn, double mx_padded, double res) {
-  const double c = __builtin_ceil((mx_padded - mn) / res);
-  return c >= 0.0 && c <= (double)DP_FLOOR_MAX_DIM ? (int)c : -1;
-}
-// a packed row's last word: the bits below W
-__device__ __forceinline__ u64 tail_mask(int W) { return (W & 63) ? ((1ull << (W & 63)) - 1) : ~0ull; }
 
 __device__ __forceinline__ bool fin(double v) { return __builtin_fabs(v) < __builtin_inf(); }   // false for NaN, +-inf
 __device__ __forceinline__ bool finite3(double x, double y, double z) { return fin(x) && fin(y) && fin(z); }

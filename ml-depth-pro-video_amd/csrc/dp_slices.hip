@@ -5,8 +5,10 @@
 // method.  Every per-cell buffer is [S][max_cells]: slice s begins at s * max_cells, its live size is dims[s].
 // A per-cell kernel is launched with the slice in blockIdx.y, so the lanes of a wave share their slice.
 // fp64 with no FMA contraction where coordinates are involved.  No kernel waits on another workgroup.
+// The extent rule, the raster's wave join, the packed morphology and the linking of the components are shared
+// with the single floor plan and live in dp_grid2.h.
 #include "dp_common.h"
-#include "dp_points.h"
+#include "dp_grid2.h"
 
 #pragma clang fp contract(off)
 
@@ -15,7 +17,6 @@ namespace {
 constexpr int GRID_CAP = 4096;                  // workgroups of a per-point kernel at the most
 constexpr int CELL_CAP = 1024;                  // workgroups per slice of a per-cell kernel at the most
 #define SMAX DP_SLICE_MAX
-constexpr uint32_t NO_CELL = ~0u;
 
 struct SliceHdr {
   u64 mm[4];                      // keys of min / max of x, z over the slice's participants
@@ -100,11 +101,7 @@ __global__ void slice_setup_kernel(SliceHdr* h, int S, double res, double paddin
   if (q.part == 0 || (long long)q.part < (long long)min_points) {
     err = 1;
   } else {
-    ox = unkey(q.mm[0]) - padding;
-    oz = unkey(q.mm[2]) - padding;
-    W = axis_cells(ox, unkey(q.mm[1]) + padding, res);
-    H = axis_cells(oz, unkey(q.mm[3]) + padding, res);
-    if (W < 0 || H < 0 || (long long)W * H > max_cells) { err = 2; H = 0; W = 0; }
+    err = grid_extent(q.mm, padding, res, max_cells, ox, oz, H, W);
   }
   q.ox = ox; q.oz = oz; q.err = (uint32_t)err;
   q.H = dims[2 * s] = H;
@@ -124,8 +121,8 @@ __global__ void __launch_bounds__(256) slice_clear_kernel(const SliceHdr* h, int
   }
 }
 
-// Pass 2: the joining loop of dp_floorplan.hip's raster with the key (slice, cell).  The slices are taken one
-// after the other, so two rows join only inside one slice; a row of two slices is rastered into both.
+// Pass 2: the wave join of dp_grid2.h with the key (slice, cell).  The slices are taken one after the other,
+// so two rows join only inside one slice; a row of two slices is rastered into both.
 __global__ void __launch_bounds__(256) slice_raster_kernel(const double* __restrict__ pts, const int32_t* n_dev, int n_max, int S,
                                                            double res, SliceHdr* h, int max_cells, uint32_t* __restrict__ keys,
                                                            uint32_t* __restrict__ density) {
@@ -163,24 +160,7 @@ __global__ void __launch_bounds__(256) slice_raster_kernel(const double* __restr
       const u64 out = __ballot(in && !valid);
       if (out && lane == 0) atomicAdd(&h[s].dropped, (uint32_t)__popcll(out));
       const size_t at = (size_t)s * max_cells;
-      u64 todo = __ballot(valid);
-      while (todo) {
-        const int leader = __ffsll((long long)todo) - 1;
-        const int lc = __shfl(cell, leader);
-        const bool mine = valid && cell == lc;
-        const u64 m = __ballot(mine);
-        uint32_t k = mine ? key : 0u;
-        #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-          const uint32_t t = __shfl_xor(k, o);
-          k = t > k ? t : k;
-        }
-        if (lane == leader) {
-          atomicAdd(&density[at + lc], (uint32_t)__popcll(m));
-          atomicMax(&keys[at + lc], k);
-        }
-        todo &= ~m;
-      }
+      wave_join_cells(valid, cell, key, density + at, keys + at);
     }
   }
 }
@@ -217,45 +197,6 @@ __global__ void cc_zero_kernel(SliceHdr* h, int S) {
   if ((int)threadIdx.x < S) h[threadIdx.x].fg = h[threadIdx.x].roots = 0;
 }
 
-__global__ void __launch_bounds__(256) cc_init_kernel(const uint8_t* __restrict__ grid, const int32_t* dims, int max_cells,
-                                                      uint32_t* __restrict__ parent, SliceHdr* h) {
-  const int s = blockIdx.y;
-  int H, W;
-  grid_dims(dims + 2 * s, max_cells, H, W);
-  const long long cells = (long long)H * W;
-  const size_t at = (size_t)s * max_cells;
-  for (long long b = (long long)blockIdx.x * 256; b < cells; b += (long long)gridDim.x * 256) {
-    const long long c = b + threadIdx.x;
-    const bool fg = c < cells && grid[at + c] != 0;
-    if (c < cells) parent[at + c] = fg ? (uint32_t)(at + c) : NO_CELL;
-    wave_count(&h[s].fg, fg);
-  }
-}
-
-// the stacked cell index s * max_cells + c is the union-find's element; a cell is joined to its west,
-// north-west, north and north-east neighbours inside its slice's dims, so no set spans two slices
-__global__ void __launch_bounds__(256) cc_link_kernel(const uint8_t* __restrict__ grid, const int32_t* dims, int max_cells,
-                                                      uint32_t* __restrict__ parent) {
-  const int s = blockIdx.y;
-  int H, W;
-  grid_dims(dims + 2 * s, max_cells, H, W);
-  const long long cells = (long long)H * W;
-  const size_t at = (size_t)s * max_cells;
-  const uint8_t* g = grid + at;
-  for (long long c = (long long)blockIdx.x * 256 + threadIdx.x; c < cells; c += (long long)gridDim.x * 256) {
-    if (!g[c]) continue;
-    const int r = (int)(c / W), x = (int)(c % W);
-    const uint32_t me = (uint32_t)(at + c);
-    if (x > 0 && g[c - 1]) uf_unite(parent, me, me - 1);
-    if (r > 0) {
-      const long long up = c - W;
-      if (x > 0 && g[up - 1]) uf_unite(parent, me, me - (uint32_t)W - 1);
-      if (g[up]) uf_unite(parent, me, me - (uint32_t)W);
-      if (x + 1 < W && g[up + 1]) uf_unite(parent, me, me - (uint32_t)W + 1);
-    }
-  }
-}
-
 // after the last union a set cell is a root iff it is its own parent (halving only rewrites other words)
 __global__ void __launch_bounds__(256) cc_roots_kernel(const int32_t* dims, int max_cells, const uint32_t* __restrict__ parent,
                                                        SliceHdr* h) {
@@ -284,106 +225,12 @@ __global__ void cc_sizes_kernel(const SliceHdr* h, int S, int32_t* __restrict__ 
   counts[2 * s] = cells; counts[2 * s + 1] = comps;
 }
 
-// ---- morphology: dp_floorplan.hip's packed passes with the slice in blockIdx.y and the radius per slice ----
-// M1: a size that is not odd or not in [1, DP_FLOOR_MAX_KERNEL] is read as 1
-__device__ __forceinline__ int slice_rad(const int32_t* size_dev, int s, int rad_host) {
-  if (!size_dev) return rad_host;
-  const int k = size_dev[s];
-  return (k >= 1 && k <= DP_FLOOR_MAX_KERNEL && (k & 1)) ? k / 2 : 0;
-}
-
-__global__ void __launch_bounds__(256) slice_pack_kernel(const uint8_t* __restrict__ grid, const int32_t* dims, int max_cells,
-                                                         long long words_cap, u64* __restrict__ bits) {
-  const int s = blockIdx.y;
-  int H, W;
-  grid_dims(dims + 2 * s, max_cells, H, W);
-  const int WW = (W + 63) >> 6, lane = threadIdx.x & 63;
-  const long long words = (long long)H * WW;
-  const uint8_t* g = grid + (size_t)s * max_cells;
-  u64* out = bits + (size_t)s * words_cap;
-  for (long long t = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); t < words; t += (long long)gridDim.x * 4) {
-    const int r = (int)(t / WW), gx = (int)(t % WW) * 64 + lane;
-    const u64 w = __ballot(gx < W && g[(long long)r * W + gx] != 0);
-    if (lane == 0) out[t] = w;
-  }
-}
-
-__global__ void __launch_bounds__(256) slice_unpack_kernel(const u64* __restrict__ bits, const int32_t* dims, int max_cells,
-                                                           long long words_cap, uint8_t* __restrict__ grid) {
-  const int s = blockIdx.y;
-  int H, W;
-  grid_dims(dims + 2 * s, max_cells, H, W);
-  const int WW = (W + 63) >> 6;
-  const long long cells = (long long)H * W;
-  const u64* in = bits + (size_t)s * words_cap;
-  uint8_t* g = grid + (size_t)s * max_cells;
-  for (long long c = (long long)blockIdx.x * 256 + threadIdx.x; c < cells; c += (long long)gridDim.x * 256) {
-    const int r = (int)(c / W), gx = (int)(c % W);
-    g[c] = (uint8_t)((in[(long long)r * WW + (gx >> 6)] >> (gx & 63)) & 1);
-  }
-}
-
-__global__ void __launch_bounds__(256) slice_morph_h_kernel(const u64* __restrict__ src_all, u64* __restrict__ dst_all,
-                                                            const int32_t* dims, int max_cells, long long words_cap,
-                                                            const int32_t* size_dev, int rad_host, int erode) {
-  const int s = blockIdx.y;
-  int H, W;
-  grid_dims(dims + 2 * s, max_cells, H, W);
-  const int WW = (W + 63) >> 6, rad = slice_rad(size_dev, s, rad_host);
-  const long long words = (long long)H * WW;
-  const u64* src = src_all + (size_t)s * words_cap;
-  u64* dst = dst_all + (size_t)s * words_cap;
-  const u64 fill = erode ? ~0ull : 0ull, tail = tail_mask(W);
-  for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < words; t += (long long)gridDim.x * 256) {
-    const int j = (int)(t % WW);
-    u64 C = src[t];
-    if (j == WW - 1) C = (C & tail) | (fill & ~tail);
-    const u64 L = j > 0 ? src[t - 1] : fill;
-    u64 R = fill;
-    if (j + 1 < WW) {
-      R = src[t + 1];
-      if (j + 1 == WW - 1) R = (R & tail) | (fill & ~tail);
-    }
-    u64 acc = C;
-    for (int k = 1; k <= rad; ++k) {
-      const u64 a = (C >> k) | (R << (64 - k)), b = (C << k) | (L >> (64 - k));
-      acc = erode ? (acc & a & b) : (acc | a | b);
-    }
-    dst[t] = j == WW - 1 ? (acc & tail) : acc;
-  }
-}
-
-__global__ void __launch_bounds__(256) slice_morph_v_kernel(const u64* __restrict__ src_all, u64* __restrict__ dst_all,
-                                                            const int32_t* dims, int max_cells, long long words_cap,
-                                                            const int32_t* size_dev, int rad_host, int erode) {
-  const int s = blockIdx.y;
-  int H, W;
-  grid_dims(dims + 2 * s, max_cells, H, W);
-  const int WW = (W + 63) >> 6, rad = slice_rad(size_dev, s, rad_host);
-  const long long words = (long long)H * WW;
-  const u64* src = src_all + (size_t)s * words_cap;
-  u64* dst = dst_all + (size_t)s * words_cap;
-  for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < words; t += (long long)gridDim.x * 256) {
-    const int r = (int)(t / WW);
-    u64 acc = src[t];
-    for (int d = -rad; d <= rad; ++d) {
-      const int rr = r + d;
-      if (d == 0 || rr < 0 || rr >= H) continue;
-      const u64 w = src[t + (long long)d * WW];
-      acc = erode ? (acc & w) : (acc | w);
-    }
-    dst[t] = acc;
-  }
-}
-
 // ---- workspace ------------------------------------------------------------------------------------
 struct Ws {
   SliceHdr* h;
   uint32_t* parent;
   u64 *bits_a, *bits_b;
 };
-// words of a packed grid: H * ceil(W / 64) <= (H W + 63 H) / 64
-int64_t bit_words_for(int64_t cells) { return cells / 64 + DP_FLOOR_MAX_DIM + 1; }
 int64_t ws_bytes_for(int64_t S, int64_t max_cells) {
   const int64_t k = S < 0 ? 0 : (S > SMAX ? SMAX : S), n = max_cells < 0 ? 0 : max_cells;
   return al256(sizeof(SliceHdr) * SMAX) + al256(4 * k * n) + 2 * al256(8 * k * bit_words_for(n)) + 256;
@@ -397,9 +244,7 @@ bool ws_carve(void* ws, int64_t bytes, int64_t S, int64_t max_cells, Ws* o) {
   o->bits_b = (u64*)p;
   return true;
 }
-bool pos_finite(double v) { return v > 0.0 && v < __builtin_inf(); }
 bool finite_h(double v) { return __builtin_fabs(v) < __builtin_inf(); }
-bool kernel_size_ok(int k) { return k >= 1 && k <= DP_FLOOR_MAX_KERNEL && (k & 1); }
 // S in [1, DP_SLICE_MAX], and the stacked cell index below 2^31
 bool layout_ok(int S, int max_cells) { return S >= 1 && S <= SMAX && max_cells >= 0 && (int64_t)S * max_cells <= 0x7fffffffll; }
 
@@ -448,7 +293,7 @@ extern "C" int dp_slice_closing_sizes(const uint8_t* grid, const int32_t* dims, 
   const int S = num_slices;
   const dim3 gc(grid_for(max_cells, CELL_CAP), S);
   hipLaunchKernelGGL(cc_zero_kernel, dim3(1), dim3(64), 0, s, w.h, S);
-  hipLaunchKernelGGL(cc_init_kernel, gc, dim3(256), 0, s, grid, dims, max_cells, w.parent, w.h);
+  hipLaunchKernelGGL(cc_init_kernel, gc, dim3(256), 0, s, grid, dims, max_cells, w.parent, &w.h->fg, (int)(sizeof(SliceHdr) / 4));
   hipLaunchKernelGGL(cc_link_kernel, gc, dim3(256), 0, s, grid, dims, max_cells, w.parent);
   hipLaunchKernelGGL(cc_roots_kernel, gc, dim3(256), 0, s, dims, max_cells, w.parent, w.h);
   hipLaunchKernelGGL(cc_sizes_kernel, dim3(1), dim3(64), 0, s, w.h, S, close_size_out, (long long*)counts_out);
@@ -463,20 +308,8 @@ extern "C" int dp_slice_morphology(const uint8_t* grid, const int32_t* dims, int
   if (!layout_ok(num_slices, max_cells) || close_iters < 0 || !kernel_size_ok(open_size)) return DP_ERR_SHAPE;
   Ws w;
   if (!ws_carve(workspace, workspace_bytes, num_slices, max_cells, &w)) return DP_ERR_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  const int S = num_slices;
-  const long long words = bit_words_for(max_cells);
-  const dim3 gw(grid_for(words, CELL_CAP), S), gc(grid_for(max_cells, CELL_CAP), S), gk(grid_for(64 * words, CELL_CAP), S);
-  u64 *a = w.bits_a, *b = w.bits_b;
-  hipLaunchKernelGGL(slice_pack_kernel, gk, dim3(256), 0, s, grid, dims, max_cells, words, a);
-  // one dilation or erosion by a square: the row pass, then the column pass; size_dev: the per-slice sizes, or NULL
-  auto pass = [&](const int32_t* size_dev, int rad, int erode) {
-    hipLaunchKernelGGL(slice_morph_h_kernel, gw, dim3(256), 0, s, a, b, dims, max_cells, words, size_dev, rad, erode);
-    hipLaunchKernelGGL(slice_morph_v_kernel, gw, dim3(256), 0, s, b, a, dims, max_cells, words, size_dev, rad, erode);
-  };
-  for (int it = 0; it < close_iters; ++it) { pass(close_size, 0, 0); pass(close_size, 0, 1); }
-  if (open_size > 1) { pass(nullptr, open_size / 2, 1); pass(nullptr, open_size / 2, 0); }
-  hipLaunchKernelGGL(slice_unpack_kernel, gc, dim3(256), 0, s, a, dims, max_cells, words, grid_out);
+  morphology_launch((hipStream_t)stream, grid, dims, num_slices, max_cells, close_size, 1, close_iters, open_size, grid_out, w.bits_a,
+                    w.bits_b, CELL_CAP);
   DP_CHECK_LAUNCH();
   return 0;
 }

@@ -464,6 +464,29 @@ def test_morphology_with_device_sizes(cuda):
 
 
 @pytest.mark.gpu
+def test_morphology_full_word_rows_inside_a_stack(cuda):
+    """Rows of 63, 64 and 65 cells (the last word one bit short, exactly full, one bit into the next) stacked so that the
+    full-word grid sits at a non-zero slice: the tail mask beside the slice's cell and word offsets."""
+    import torch
+
+    from depth_pro import pointcloud as PC
+
+    fg = np.load(os.path.join(GOLDEN, "golden_floorplan.npz"))
+    sizes, mc = [7, 3, 11, 5], 37 * 65 + 5
+    for names in (("random_37x63", "random_37x64", "random_37x65", "random_1x1"), ("random_37x63", "holes_37x64", "frame_37x65", "random_1x1")):
+        grids = [fg[f"morph_{n}"] for n in names]
+        assert [g.shape for g in grids] == [(37, 63), (37, 64), (37, 65), (1, 1)]
+        stack, dims = _stack(grids, mc)
+        out = torch.full((4 * mc + 64,), GUARD8, dtype=torch.uint8, device=cuda)
+        PC.slice_morphology(_dev(stack, cuda), _dev(dims, cuda), _dev(np.array(sizes, np.int32), cuda), 1, 3, out=out[:4 * mc].view(4, mc))
+        host = out.cpu().numpy()
+        assert (host[4 * mc:] == GUARD8).all()
+        for s, grid in enumerate(grids):
+            assert np.array_equal(host[s * mc:s * mc + grid.size].reshape(grid.shape), FN.morphology(grid, sizes[s], 1, 3)), (names, s)
+            assert (host[s * mc + grid.size:(s + 1) * mc] == GUARD8).all(), (names, s)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("name", OUTLINE_FIXTURES)
 def test_simplify_outlines_with(name, cuda):
     import torch

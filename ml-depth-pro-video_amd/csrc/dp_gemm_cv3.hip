@@ -512,6 +512,8 @@ int launch_cv3(const GemmP& p0, hipStream_t s, int th) {
   const int S = p.out_w;
   // the composed head's compact form (4 taps per parity): recognised by its K
   const bool cpt = p.store_mode == DP_STORE_HEAD_PS && p.K == 4 * p.in_c;
+  // (the checks down to `th == 24` are a defensive re-check on the GemmP: what the engine takes is
+  // stated in serves_cv3, dp_gemm.hip)
   if (!cpt && p.K != 9 * p.in_c) return DP_ERR_ARG;
   if (cpt && (p.relu_a || th == 12)) return DP_ERR_ARG;
   if (p.k_h != 3 || p.k_w != 3 || p.stride != 1 || p.pad != 1 || p.in_h != S || p.in_w != S || p.out_h != S ||
@@ -538,10 +540,10 @@ int launch_cv3(const GemmP& p0, hipStream_t s, int th) {
   p.tiles_n = p.N / bn;
   p.tiles_m = (p.M / (S * S)) * (S / th) * (S / CV_TW);
   dim3 grid(p.tiles_m * p.tiles_n);
-  // K-loop ablation / stamp variants (tools/cv3_stamps.py): only with debug bit 1 << 24 set, so that
-  // the planner's own debug bits (16, 32, 64, 1024, ...) never select one; an ablation
+  // K-loop ablation / stamp variants (tools/cv3_stamps.py): only with DBG_CV3_ABLATION set, so that
+  // the planner's own debug bits (DBG_NO_SMALL_STREAMK, DBG_NO_PBIG, ...) never select one; an ablation
   // value without a variant runs the normal kernel
-  const int abl = (p.dbg & (1 << 24)) ? p.dbg & 2047 : 0;
+  const int abl = (p.dbg & DBG_CV3_ABLATION) ? p.dbg & DBG_CV3_ABLATION_MASK : 0;
   if (cpt) {
     if (th == 24) hipLaunchKernelGGL((gemm_cv3_kernel<K_, false, 128, CV_EPI_HPS, 0, 24, 4>), grid, dim3(512), 0, s, p);
     else hipLaunchKernelGGL((gemm_cv3_kernel<K_, false, 128, CV_EPI_HPS, 0, 16, 4>), grid, dim3(512), 0, s, p);

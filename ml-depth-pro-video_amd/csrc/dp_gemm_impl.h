@@ -68,7 +68,7 @@ struct GemmP {
   float head_b;
   const float* head_corr;
   int tiles_n, tiles_m;
-  int dbg;  // ablation bits for tools/gemm_bench.py: 1 no stores, 2 no loads in loop, 4 no MFMA
+  int dbg;  // ablation / A-B bits (DBG_* below)
   unsigned c_bytes;  // persistent engine: byte extent of C from p.C (buffer-store bound)
   // LayerNorm folded across the GEMM boundary (dp_gemm_args.ln_*; the 8-phase 320 x 256 engine)
   float* ln_part_out;      // producer: (mean, M2) per 128-column chunk of the new C rows
@@ -106,8 +106,73 @@ struct GemmP {
 // Process-wide ablation / fault-injection bits (dp_gemm.hip), set only by dp_gemm_debug_flags
 // (tools and tests; not in the ABI header).  Read once per dp_gemm call.
 extern std::atomic<int> g_dbg_flags;
+// The bits (GemmP::dbg).  Tools and tests pass the integers; every reader uses these names.
+enum : int {
+  DBG_NO_EPILOGUE = 1,              // kernels skip the epilogue (tools/gemm_bench.py --ablate, head_bench.py, hilo_bench.py)
+  DBG_NO_LOOP_LOADS = 2,            // big engine: no loads in the K loop (tools/gemm_bench.py --ablate)
+  DBG_NO_MFMA = 4,                  // big engine: no MFMAs in the K loop (tools/gemm_bench.py --ablate)
+  DBG_ROW_MAJOR_TILES = 16,         // tile_coords: row-major instead of 4-row bands (tools/gemm_bench.py --dbg 16)
+  DBG_NO_SMALL_STREAMK = 32,        // planner + sk_grid: no stream-K K split for small conv grids (tools/frame_shapes.py --dbg 32)
+  DBG_SK_GIVE_UP = 64,              // stream-K: a waiting workgroup gives up at once (tests: the sticky error word)
+  DBG_NO_PBIG = 1024,               // planner: no persistent 320 x 256 / 256 x 256 upgrade (DP_GEMM_DEBUG, tools/ab_bench.sh)
+  DBG_PBIG_DENSE = 2048,            // planner: the persistent upgrade for dense (ViT) GEMMs too (DP_GEMM_DEBUG, tools/ab_bench.sh)
+  DBG_NO_CV3_HEAD = 4096,           // planner: the N = 128 head conv on the 512 x 128 engine (tests/test_abi.py, tools/head_bench.py)
+  DBG_FC1_BIG320 = 8192,            // planner: the 8-phase choice (fc1) -> 320 x 256 (tools/fc1_bench.py, tests/test_bench_cli.py)
+  DBG_FC1_BIG256 = 16384,           // planner: the 8-phase choice (fc1) -> 256 x 256 (tools/fc1_bench.py)
+  DBG_NO_8PH320 = 1 << 15,          // planner: no 8-phase 320 x 256 upgrade (DP_GEMM_DEBUG, tools/ab_bench.sh)
+  DBG_NO_CV3 = 1 << 16,             // planner: no patch-conv upgrade of the 3x3 convs (DP_GEMM_DEBUG, tools/ab_bench.sh)
+  DBG_BAND8 = 1 << 18,              // tile_coords: bands of 8 tile rows (tools/p8ph_stamps.py)
+  DBG_BAND2 = 1 << 19,              // tile_coords: bands of 2 tile rows (tools/p8ph_stamps.py)
+  DBG_NO_FAST_EPILOGUE = 1 << 20,   // no load-free epilogues, so no P8PH / 8PH_320x256 engine (DP_GEMM_DEBUG, tools/ab_bench.sh)
+  DBG_NO_P8PH = 1 << 22,            // planner: no persistent upgrade of the 8-phase engine (DP_GEMM_DEBUG, tools/ab_bench.sh)
+  DBG_NO_P8PH_DECONV = 1 << 23,     // planner: the deconvs not on the persistent 8-phase engine (tests/test_abi.py)
+  DBG_CV3_ABLATION = 1 << 24,       // launch_cv3: bits 0..10 select a K-loop ablation / stamp variant (tools/cv3_stamps.py)
+  DBG_LNC_8PH320 = 1 << 25,         // planner: folded-LN consumers on the 320 x 256 engine (DP_GEMM_DEBUG, tools/ab_bench.sh)
+  DBG_HILO_AHEAD1 = 1 << 27,        // split-residual producer: the one-chunk-ahead epilogue (tools/hilo_bench.py, tests/test_gpu_kernels.py)
+};
+constexpr int DBG_CV3_ABLATION_MASK = 2047;   // the variant number under DBG_CV3_ABLATION
 // CU count of the current device (cached, dp_gemm.hip)
 int num_cus();
+
+// The engines by DP_TILE_* value: tile rows x columns, the family (translation unit) that launches
+// it, whether the grid is capped at the CU count (persistent workgroups), and whether the epilogue
+// works on 8-column chunks (dp_mi355x.h: the 8-column rules).
+enum TileFamily { FAM_NONE, FAM_SMALL, FAM_BIG, FAM_BIG320, FAM_8PH, FAM_8PH320, FAM_PBIG, FAM_SK, FAM_SPLITK, FAM_CV3 };
+struct TileInfo {
+  int bm, bn;
+  TileFamily fam;
+  bool cu_capped, col8;
+};
+constexpr TileInfo TILES[] = {
+    {0, 0, FAM_NONE, false, false},        // DP_TILE_AUTO
+    {128, 128, FAM_SMALL, false, false},   // DP_TILE_128x128
+    {256, 64, FAM_SMALL, false, false},    // DP_TILE_256x64
+    {256, 32, FAM_SMALL, false, false},    // DP_TILE_256x32
+    {256, 256, FAM_BIG, false, true},      // DP_TILE_BIG_256x256
+    {256, 128, FAM_BIG, false, true},      // DP_TILE_BIG_256x128
+    {256, 256, FAM_BIG, false, true},      // DP_TILE_BIG_256x256_K32
+    {256, 128, FAM_BIG, false, true},      // DP_TILE_BIG_256x128_K32
+    {256, 256, FAM_8PH, false, true},      // DP_TILE_8PH_256x256
+    {256, 256, FAM_BIG, false, true},      // DP_TILE_DEEP4_256x256
+    {256, 256, FAM_BIG, false, true},      // DP_TILE_DEEP5_256x256
+    {256, 128, FAM_BIG, false, true},      // DP_TILE_DEEP_256x128
+    {256, 256, FAM_SK, false, true},       // DP_TILE_STREAMK_256x256 (grid: sk_grid)
+    {320, 256, FAM_BIG320, false, true},   // DP_TILE_BIG_320x256
+    {512, 128, FAM_BIG320, false, true},   // DP_TILE_BIG_512x128
+    {320, 256, FAM_PBIG, true, true},      // DP_TILE_PBIG_320x256
+    {256, 256, FAM_PBIG, true, true},      // DP_TILE_PBIG_256x256
+    {256, 128, FAM_SMALL, false, true},    // DP_TILE_DUAL_256x128
+    {256, 256, FAM_8PH, true, true},       // DP_TILE_P8PH_256x256
+    {320, 256, FAM_8PH320, false, true},   // DP_TILE_8PH_320x256
+    {256, 256, FAM_CV3, false, true},      // DP_TILE_CV3_256x256 (16 x 16 pixels)
+    {256, 256, FAM_SPLITK, false, true},   // DP_TILE_SPLITK_256x256 (grid: x the K split)
+    {192, 256, FAM_CV3, false, true},      // DP_TILE_CV3_192x256 (12 x 16 pixels)
+    {384, 128, FAM_CV3, false, true},      // DP_TILE_CV3_384x128 (24 x 16 pixels)
+};
+constexpr int N_TILES = sizeof(TILES) / sizeof(TILES[0]);
+static_assert(N_TILES == 24 && DP_TILE_CV3_384x128 == N_TILES - 1, "one entry per DP_TILE_*");
+// (a hint outside the enum plans and runs as DP_TILE_BIG_256x256, the big engine's default instantiation)
+inline const TileInfo& tile_info(int tile) { return TILES[tile >= 0 && tile < N_TILES ? tile : DP_TILE_BIG_256x256]; }
 
 // Engine families, one translation unit each: launch `p` (planned by dp_gemm.hip) on `tile`.
 int launch_part_big(const GemmP& p, int tile, bool conv, bool bf16, hipStream_t s);      // dp_gemm_big.hip
@@ -136,7 +201,7 @@ int sk_grid(const GemmP& p) {
   int g = num_cus();
   if (g > 256) g = 256;   // == SK_MAX_WG (workspace slots)
   if (tiles >= g) return g;
-  if (p.dbg & 32) return tiles;
+  if (p.dbg & DBG_NO_SMALL_STREAMK) return tiles;
   const int kt = p.K / 64;
   int s = g / tiles;
   if (s < 2) return kt >= 2 * SK_MIN_STEPS ? g : tiles;
@@ -893,7 +958,7 @@ __device__ __forceinline__ void epilogue_acc32_wide(const GemmP& p, f32x4_t (&ac
 // (fp32 C accumulated into, no other per-row operand).
 constexpr int EPI_ACC = 16;
 __host__ inline int fast_epi_act(const GemmP& p) {
-  if (p.dbg & (1 << 20)) return -1;
+  if (p.dbg & DBG_NO_FAST_EPILOGUE) return -1;
   if (!needs_rowld(p)) return p.c_dtype == DP_F32 ? -1 : p.act;
   const bool acc_only = p.accumulate && p.c_dtype == DP_F32 && !p.R1 && !p.R2 && !p.pos &&
                         p.store_mode == DP_STORE_ROWS && !p.row_group && !p.head_corr && !p.head_w;
@@ -959,7 +1024,7 @@ __device__ __forceinline__ void head_ps_rows(const GemmP& p, const ColConst& cc,
 // (tools/gemm_bench.py --dbg 16 restores row-major, for A/B).
 __device__ __forceinline__ void tile_coords(const GemmP& p, int wgid, int& tile_m, int& tile_n) {
   // debug 16: row-major; 1 << 18: bands of 8 rows; 1 << 19: bands of 2 rows (A/B)
-  const int band = (p.dbg & 16) ? 1 : (p.dbg & (1 << 18)) ? 8 : (p.dbg & (1 << 19)) ? 2 : 4;
+  const int band = (p.dbg & DBG_ROW_MAJOR_TILES) ? 1 : (p.dbg & DBG_BAND8) ? 8 : (p.dbg & DBG_BAND2) ? 2 : 4;
   const int tm_full = p.tiles_m / band * band;       // rows covered by whole bands
   const int per_band = band * p.tiles_n;
   if (band > 1 && wgid < tm_full * p.tiles_n) {
@@ -1422,11 +1487,11 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) gemm_big_kernel(cons
 #ifdef DP_STAMPS
       if (kt == 0) DP_STAMP(st1_);
 #endif
-      if (kt + NS - 1 < KT && !(p.dbg & 2)) {
+      if (kt + NS - 1 < KT && !(p.dbg & DBG_NO_LOOP_LOADS)) {
         const int st = stage + NS - 1;
         issue(kt + NS - 1, st >= NS ? st - NS : st);
       }
-      if (p.dbg & 4) {
+      if (p.dbg & DBG_NO_MFMA) {
         const u16* sa = (const u16*)(smem + stage * STAGE);
         uint4 t = *(const uint4*)(sa + lds_off_t<BKT>(wm * TM + frow, fchunk));
         asm volatile("" ::"v"(t.x));
@@ -1519,7 +1584,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) gemm_big_kernel(cons
   }
 
   DP_STAMP(st2_);
-  if (p.dbg & 1) {
+  if (p.dbg & DBG_NO_EPILOGUE) {
     #pragma unroll
     for (int i = 0; i < FM; ++i)
       #pragma unroll
@@ -1939,7 +2004,7 @@ __global__ void __launch_bounds__(512, 1) gemm_8ph_kernel(const GemmP p) {
     bar();
   }
   if (wm == 0) bar();
-  if (p.dbg & 1) {   // ablation (tools/gemm_bench.py --ablate): no epilogue
+  if (p.dbg & DBG_NO_EPILOGUE) {   // ablation (tools/gemm_bench.py --ablate): no epilogue
     #pragma unroll
     for (int i = 0; i < 8; ++i)
       #pragma unroll
@@ -2469,13 +2534,14 @@ int launch_p8ph(const GemmP& p0, hipStream_t s) {
   const int T = p.tiles_n * p.tiles_m;
   const bool dcv = p.store_mode == DP_STORE_DECONV2X2;
   const int ea = dcv ? p.act : fast_epi_act(p);
+  // (a defensive re-check on the GemmP: what the engine takes is stated in serves_p8ph, dp_gemm.hip)
   if (p.N % 256 || p.K < 128 || !p.c_bytes || p.c_dtype == DP_F32 || ea < 0 || ea >= EPI_ACC) return DP_ERR_ARG;
   int G = num_cus();
   if (G > T) G = T;
   dim3 grid(G);
   if (dcv) {   // the 2x2 stride-2 deconvs: bias only (no per-row operands, no activation)
     if (p.relu_a || p.gamma || p.pos || p.R1 || p.R2 || p.accumulate || p.row_group || p.head_w || p.head_corr ||
-        ea != DP_ACT_NONE || p.dc_cout % 8 || p.dbg & (1 << 20))
+        ea != DP_ACT_NONE || p.dc_cout % 8 || p.dbg & DBG_NO_FAST_EPILOGUE)
       return DP_ERR_ARG;
     hipLaunchKernelGGL((gemm_p8ph_kernel<K_, false, DP_ACT_NONE, false, true>), grid, dim3(512), 0, s, p);
     DP_CHECK_LAUNCH();
@@ -2673,7 +2739,7 @@ __global__ void __launch_bounds__(512, 1) gemm_8ph320_kernel(const GemmP p) {
     for (int s = 0; s < KT; ++s) step(s, s & 1);
   }
   if (wave < 4) bar();
-  if (p.dbg & 1) {   // ablation (tools/gemm_bench.py --ablate): no epilogue
+  if (p.dbg & DBG_NO_EPILOGUE) {   // ablation (tools/gemm_bench.py --ablate): no epilogue
     #pragma unroll
     for (int i = 0; i < FM; ++i)
       #pragma unroll
@@ -2701,12 +2767,13 @@ int launch_8ph320(const GemmP& p0, hipStream_t s) {
   p.tiles_n = p.N / 256;
   p.tiles_m = (p.M + 319) / 320;
   const int ea = fast_epi_act(p);
+  // (a defensive re-check on the GemmP: what the engine takes is stated in serves_8ph320, dp_gemm.hip)
   if (p.N % 256 || ea < 0 || p.relu_a) return DP_ERR_ARG;
   dim3 grid(p.tiles_n * p.tiles_m);
   if (p.ln_xl) {         // folded-LN producer on the split (hi + lo) residual stream
     if (!p.ln_xb_out || p.act != DP_ACT_NONE) return DP_ERR_ARG;
     static_assert(8 * 13312 <= 2 * (320 * 128 + 256 * 128), "hi/lo staging fits the ring");
-    if (p.dbg & (1 << 27)) hipLaunchKernelGGL((gemm_8ph320_kernel<K_, EPI_ACC + DP_ACT_NONE, 4>), grid, dim3(512), 0, s, p);
+    if (p.dbg & DBG_HILO_AHEAD1) hipLaunchKernelGGL((gemm_8ph320_kernel<K_, EPI_ACC + DP_ACT_NONE, 4>), grid, dim3(512), 0, s, p);
     else hipLaunchKernelGGL((gemm_8ph320_kernel<K_, EPI_ACC + DP_ACT_NONE, 3>), grid, dim3(512), 0, s, p);
     DP_CHECK_LAUNCH();
     return 0;
@@ -2945,8 +3012,8 @@ __global__ void __launch_bounds__(512, 1) gemm_sk_kernel(const GemmP p, const Sk
     if (tid == 0) {
       unsigned spins = 0;
       // debug bit 64 (tests only): give up at once, as a starved wait would
-      const unsigned limit = (p.dbg & 64) ? 0u : (1u << 24);
-      while (__hip_atomic_load(s.flags + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u || (p.dbg & 64)) {
+      const unsigned limit = (p.dbg & DBG_SK_GIVE_UP) ? 0u : (1u << 24);
+      while (__hip_atomic_load(s.flags + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u || (p.dbg & DBG_SK_GIVE_UP)) {
         __builtin_amdgcn_s_sleep(2);
         if (++spins > limit) {  // ~seconds: never hang the GPU; report in the sticky error word instead
           __hip_atomic_store(s.flags + 1023, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -1,6 +1,7 @@
 // dp_gemm.hip -- host side of dp_gemm: argument checks, the engine chooser (gemm_plan), the
-// C ABI entry points.  The engines live in dp_gemm_impl.h, instantiated by dp_gemm_*.hip.
+// C ABI entry points.  The engines live in dp_gemm_*.hip, one per file (the map: dp_gemm_impl.h).
 #include "dp_gemm_impl.h"
+#include "dp_ln_merge.h"
 
 namespace dpg {
 // Process-wide ablation / fault-injection bits, set only by dp_gemm_debug_flags (tools and
@@ -50,6 +51,19 @@ extern "C" int dp_gemm_debug_flags(int flags) {
 extern "C" int64_t dp_gemm_workspace_size(void) { return SK_FLAG_BYTES + (int64_t)SK_MAX_WG * SK_TILE_F * 4; }
 
 namespace {
+// Folded LayerNorm, consumer on the persistent 8-phase engine: per row (rstd, -rstd * mean) from
+// its 8 chunk statistics (K = 1024; Chan's merge, as epilogue_mfma_lnc), one thread per row.
+__global__ void __launch_bounds__(256) ln_merge_kernel(const float* __restrict__ part, int M, float eps,
+                                                       float* __restrict__ out) {
+  const int m = blockIdx.x * 256 + threadIdx.x;
+  if (m >= M) return;
+  const f32x4_t* pp = (const f32x4_t*)(part + (long long)m * 16);
+  f32x4_t c[4];
+  #pragma unroll
+  for (int i = 0; i < 4; ++i) c[i] = pp[i];
+  *(float2*)(out + 2LL * m) = ln_merge_row(c, eps);
+}
+
 // After a forward (every launch that used `ws` has ended): report the sticky error word and,
 // if it is set, clear it and every hand-off flag (a producer that published after its consumer
 // gave up leaves its flag set; the next launch would read it as a fresh hand-off).

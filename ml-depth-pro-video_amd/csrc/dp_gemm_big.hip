@@ -1,5 +1,5 @@
 // dp_gemm_big.hip: the big-tile engine at 256 x 256 / 256 x 128 (incl. grouped launches).
-#include "dp_gemm_impl.h"
+#include "dp_gemm_big.h"
 
 namespace dpg {
 int launch_part_big(const GemmP& p, int tile, bool conv, bool bf16, hipStream_t s) {

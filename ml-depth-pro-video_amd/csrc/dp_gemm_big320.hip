@@ -1,5 +1,5 @@
 // dp_gemm_big320.hip: the big-tile engine at 320 x 256 and 512 x 128.
-#include "dp_gemm_impl.h"
+#include "dp_gemm_big.h"
 
 namespace dpg {
 int launch_part_big320(const GemmP& p, int tile, bool conv, bool bf16, hipStream_t s) {

@@ -18,7 +18,7 @@
 // the patch.  The
 // epilogue (bias, ReLU, residuals R1 / R2, 16-bit C) works in the MFMA register layout, one
 // 16-pixel output row segment per fragment row.
-#include "dp_gemm_impl.h"
+#include "dp_gemm_dev.h"
 
 namespace {
 

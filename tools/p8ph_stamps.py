@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Where a tile's time goes in the persistent 8-phase engine (the ViT fc1 and qkv: folded-LN
 consumer epilogue, GELU for fc1), from per-tile s_memrealtime stamps of the timing-only build
-(`make -C ml-depth-pro-video_amd/csrc stamps` -> libdp_mi355x_stamps.so; dp_gemm_impl.h DP_STAMPS).
+(`make -C ml-depth-pro-video_amd/csrc stamps` -> libdp_mi355x_stamps.so; dp_gemm_8ph.hip under DP_STAMPS: g_p8_stamps, gemm_p8ph_kernel).
 
 Per workgroup and tile: [K loop start, K loop done, epilogue done (its stores issued)].  Reports, in
 us (100 MHz stamps), the medians over all tiles of the K loop, the epilogue (folded LN + GELU + the

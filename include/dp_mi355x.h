@@ -1810,6 +1810,83 @@ int dp_render_points(const double* points, const uint8_t* colors, const int32_t*
                      double* cameras_out, double* stats_out, void* workspace, int64_t workspace_bytes,
                      dp_stream_t stream);
 
+/*
+ * ---- Shape overlays on the plan view (ABI 20, additive; csrc/dp_overlay.hip) ----------------------------------
+ * The last step of pointcloud_pipeline.py's in_memory_pointcloud_visualization (:172-230): the fitted rectangles and
+ * circles stroked on the plan picture of dp_render_points, each with its number.  Strokes and labels are drawn on the
+ * device from the tables that are already there; everything runs on the caller's stream as separate launches, with
+ * no synchronisation and no read-back.  matplotlib's anti-aliased rasteriser is not the target: the rule below
+ * defines the picture (restated in tests/overlay_numpy.py).  All arithmetic is fp64 in the
+ * order written, every operation rounded on its own (no FMA), square root and division correctly rounded; sin and
+ * cos are the device's, taken once per shape, and the records they go into are an output of the call.
+ *
+ * The rule.
+ *   1. Frame.  Shapes live in the top-down frame u = -x, v = z of "Cluster shapes", the plan view's own x', z.  The
+ *      camera is a plan record of dp_render_points (kind 1): cx = [2], cz = [3], scale = [4], hw = [7] = (W - 1) / 2,
+ *      hh = [8] = (H - 1) / 2.  A point (u, v) is at X = (u - cx) * scale + hw, Y = hh - (v - cz) * scale; pixel (i, j)
+ *      (column i, row j) is the point (i, j).  A camera whose kind is not 1, whose degenerate word is not 0, or with
+ *      one of the five values not finite, is degenerate: nothing is listed, nothing is drawn, the error word is 2.
+ *   2. The list.  nr = min(*n_rects_dev, max_rects) rectangles (rows of dp_shape_rectangles / dp_lshape_split, fp64
+ *      [8]: cu, cv, w, h, angle in degrees, ...) in list order, then the nc rows of the shapes table (fp64 [16], rows
+ *      below min(*n_clusters_dev, max_clusters)) whose kind [0] == 2, in table order, as circles (xc, yc, r) =
+ *      columns 8..10.  A null count reads as the capacity, a negative one as 0; rows past the count are not read.
+ *      Rectangle i is record i, carries the number i + 1 and the colour i mod 8 of the rectangle palette; the k-th
+ *      circle is record nr + k, carries nr + k + 1 and the colour k mod 8 of the circle palette (palette entries
+ *      8..15).
+ *   3. Skipped.  A shape with a non-finite column among those five (three), or w, h or r < 0, or whose X, Y, a, b
+ *      (R) or box half sides ex, ey below are not finite, is skipped: flags 8, every field but kind, colour and number 0, both boxes empty.
+ *   4. Rectangle.  a = w * scale / 2, b = h * scale / 2, t = stroke / 2, c = cos(angle * pi / 180), s = sin(same)
+ *      (pi = 3.14159265358979323846).  The rectangle is w x h, centred, turned by angle counter-clockwise in (u, v),
+ *      which is clockwise in pixels.  For a pixel, dx = i - X, dy = j - Y, x' = dx * c - dy * s, y' = dx * s + dy * c:
+ *      it is on the stroke iff |x'| <= a + t and |y'| <= b + t and not (|x'| < a - t and |y'| < b - t): mitred
+ *      corners.  Stroke box: ex = |c| * (a + t) + |s| * (b + t), ey = |s| * (a + t) + |c| * (b + t),
+ *      x0 = floor(X - ex), x1 = ceil(X + ex), y0 = floor(Y - ey), y1 = ceil(Y + ey).
+ *   5. Circle.  R = r * scale, d2 = dx * dx + dy * dy, lo = max(R - t, 0): on the stroke iff lo * lo <= d2 and
+ *      d2 <= (R + t) * (R + t).  Stroke box: x0 = floor(X - (R + t)), x1 = ceil(X + (R + t)), the same in y.
+ *      A pixel outside a shape's stroke box is not on its stroke (the box is what the tiles are culled by).
+ *   6. Blending.  A stroke pixel becomes out = (A * c + (255 - A) * p + 127) / 255 per channel, integer division.
+ *      Per pixel: the rectangles in list order, then the circles; every covering shape blends in turn.
+ *   7. Labels, after all strokes, in the same order.  label_scale = L = 0: none.  A number above 9999 has no label
+ *      and is counted (flags 4).  Otherwise, with n digits: the block is (6 n - 1) L wide and 7 L high, its corner at
+ *      lx = floor(X + 0.5) - ((6 n - 1) L) / 2, ly = floor(Y + 0.5) - (7 L) / 2 (integer division); the label box is
+ *      the block grown by L on every side.  Every pixel of the box is blended with white at A = 179; then the pixel
+ *      (lx + ox, ly + oy) of the block with column q = ox / L, digit q / 6 (most significant first), q % 6 = 5 being
+ *      the gap, is set to the shape's colour where bit 4 - q % 6 of row oy / L of the digit's 5 x 7 bitmap
+ *      (DP_OVERLAY_FONT) is set.
+ *   8. A shape whose stroke box and label box both miss the picture [0, W - 1] x [0, H - 1] is off-screen: counted,
+ *      never drawn.  flags: 1 the stroke box meets the picture, 2 the label box does, 4 label dropped, 8 skipped.
+ *   records_out  device fp64 [max_rects + max_circles][DP_OVERLAY_RECORD_DOUBLES], the first nr + nc rows written:
+ *                kind (1 rectangle, 2 circle), flags, X, Y, a (circle: R), b (0), c (1), s (0), colour r + 256 g +
+ *                65536 b, number, stroke box x0 y0 x1 y1, label box x0 y0 x1 y1, digits, 0.  An empty box is 0 0 -1 -1.
+ *   stats_out    device fp64 [DP_OVERLAY_STATS]: rectangles drawn, circles drawn (flags 1 or 2), skipped, off-screen,
+ *                labels dropped, pixels painted (covered by a stroke or a label box), error word (1: a shape was
+ *                skipped, 2: degenerate camera), 0.  The first four add up to nr + nc.
+ *   image        uint8 [H][W][3], read and written in place; a 64 x 16 tile that no record touches is not written
+ *   palette      HOST uint8 [16][3], read during the call      workspace  >= dp_overlay_workspace_size(max_rects,
+ *                max_circles) bytes (0 for negative capacities), 8-byte aligned, owned by the call until the stream
+ *                has passed it
+ * Either list may be null with a capacity of 0 (max_circles = max_clusters).  DP_ERR_ARG before any launch: a null
+ * image, camera, palette, records_out, stats_out or workspace, a null list with a capacity > 0, a double array that
+ * is not 8-byte aligned or a count that is not 4-byte aligned, W or H < 1, W * H >= 2^31, stroke not finite or not
+ * > 0, alpha outside 0..255, label_scale outside 0..DP_OVERLAY_MAX_LABEL_SCALE, a negative capacity, capacities
+ * that add up to 2^31 or more, a workspace that is short or misaligned.
+ */
+#define DP_OVERLAY_RECORD_DOUBLES   20
+#define DP_OVERLAY_STATS            8
+#define DP_OVERLAY_MAX_LABEL_SCALE  8
+#define DP_OVERLAY_LABEL_ALPHA      179
+/* the ten digits, 5 x 7, row by row from the top, bit 4 = the leftmost column */
+#define DP_OVERLAY_FONT {{14, 17, 19, 21, 25, 17, 14}, {4, 12, 4, 4, 4, 4, 14}, {14, 17, 1, 2, 4, 8, 31}, \
+                         {31, 2, 4, 2, 1, 17, 14}, {2, 6, 10, 18, 31, 2, 2}, {31, 16, 30, 1, 1, 17, 14}, \
+                         {6, 8, 16, 30, 17, 17, 14}, {31, 1, 2, 4, 8, 8, 8}, {14, 17, 17, 14, 17, 17, 14}, \
+                         {14, 17, 17, 15, 1, 2, 12}}
+int64_t dp_overlay_workspace_size(int64_t max_rects, int64_t max_circles);
+int dp_overlay_shapes(uint8_t* image, int32_t W, int32_t H, const double* camera_dev, const double* rects,
+                      const int32_t* n_rects_dev, int32_t max_rects, const double* shapes, const int32_t* n_clusters_dev,
+                      int32_t max_clusters, const uint8_t* palette, double stroke, int32_t alpha, int32_t label_scale,
+                      double* records_out, double* stats_out, void* workspace, int64_t workspace_bytes,
+                      dp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

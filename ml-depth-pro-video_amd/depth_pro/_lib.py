@@ -39,6 +39,7 @@ DP_WARP_MAX_VIEWS, DP_WARP_MAX_DIM = 32, 16384
 DP_WARP_SHIFT, DP_WARP_SHIFT_F32, DP_WARP_ZOOM = 0, 1, 2
 DP_SHADOW_STATS = 9
 DP_RENDER_MAX_VIEWS, DP_RENDER_MAX_SIZE, DP_RENDER_CAMERA_DOUBLES, DP_RENDER_STATS, DP_RENDER_STAT_VIEWS = 4, 15, 24, 24, 4
+DP_OVERLAY_RECORD_DOUBLES, DP_OVERLAY_STATS, DP_OVERLAY_MAX_LABEL_SCALE = 20, 8, 8
 DP_ABI_VERSION = 20
 
 _ERRORS = {1000: "DP_ERR_ARG", 1001: "DP_ERR_SHAPE", 1002: "DP_ERR_ALIGN", 1003: "DP_ERR_DTYPE"}
@@ -70,6 +71,7 @@ EXPORTS = (
     "dp_shadows_workspace_size", "dp_depth_gradient", "dp_depth_edges", "dp_region_filter", "dp_depth_shadows",
     "dp_fill_ground_shadows",
     "dp_render_workspace_size", "dp_render_cameras", "dp_render_points",
+    "dp_overlay_workspace_size", "dp_overlay_shapes",
 )
 
 
@@ -212,6 +214,8 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "dp_render_cameras": [vp, vp, i32, ctypes.POINTER(f64), i32, i32, f64, i32, i32, f64, vp, vp, vp, i64, vp],
         "dp_render_points": [vp, vp, vp, i32, ctypes.POINTER(f64), i32, i32, f64, i32, i32, i32, ctypes.POINTER(ctypes.c_uint8), f64,
                              i32, vp, vp, vp, vp, i64, vp],
+        "dp_overlay_workspace_size": [i64, i64],
+        "dp_overlay_shapes": [vp, i32, i32, vp, vp, vp, i32, vp, vp, i32, ctypes.POINTER(ctypes.c_uint8), f64, i32, i32, vp, vp, vp, i64, vp],
     }
     for name, argtypes in sig.items():
         fn = getattr(lib, name)
@@ -232,8 +236,11 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.dp_effects_workspace_size.restype = ctypes.c_int64
     lib.dp_shadows_workspace_size.restype = ctypes.c_int64
     lib.dp_render_workspace_size.restype = ctypes.c_int64
+    lib.dp_overlay_workspace_size.restype = ctypes.c_int64
     lib.dp_render_debug_flags.argtypes = [ctypes.c_int]
     lib.dp_render_debug_flags.restype = ctypes.c_int
+    lib.dp_overlay_debug_flags.argtypes = [ctypes.c_int]
+    lib.dp_overlay_debug_flags.restype = ctypes.c_int
     lib.dp_gemm_debug_flags.argtypes = [ctypes.c_int]
     lib.dp_gemm_debug_flags.restype = ctypes.c_int
     ver = lib.dp_abi_version()

@@ -14,8 +14,8 @@ of the reference and of this project), looking up at the underside of the floor,
 down"; here `top` looks down, so the highest point hides the one below it.  The other three presets are the reference's
 (its isometric view, front [1, -1, -1], looks from below as the reference's does).  No lighting (it changes nothing for
 points without normals); no text labels on the sheet; the plan view has no alpha blending, no random thinning to 50 000
-points and no shape overlays, it shows every point with the highest on top; mesh rendering (`visualize_mesh`) is not
-built.
+points, it shows every point with the highest on top (the shape overlays and number labels of that picture are
+`depth_pro.overlay`); mesh rendering (`visualize_mesh`) is not built.
 """
 
 from __future__ import annotations

@@ -42,6 +42,7 @@ from depth_pro import effects as FX  # noqa: E402
 from depth_pro import pointcloud as PC  # noqa: E402
 from depth_pro import shadows as SH  # noqa: E402
 from depth_pro import render as RV  # noqa: E402
+from depth_pro import overlay as OV  # noqa: E402
 
 
 def colorize_depth(depth, min_depth=None, max_depth=None, cmap="turbo"):
@@ -256,6 +257,8 @@ shadows_name = partial(frame_file, suffix="_shadows.png")               # --dept
 shadows_json_name = partial(frame_file, suffix="_shadows.json")
 view_name = partial(frame_file, suffix="_view.png")                     # --render_view; cameras and counts beside it
 view_json_name = partial(frame_file, suffix="_view.json")
+plan_name = partial(frame_file, suffix="_plan.png")                     # --plan_shapes; parameters, camera and counts beside it
+plan_json_name = partial(frame_file, suffix="_plan.json")
 
 
 def cloud_name(image_path: str, cleaned: bool = False) -> str:
@@ -330,7 +333,8 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
                               floor_slice_resolution=0.05, floor_slice_min_area=0.1, anaglyph=False,
                               anaglyph_separation=0.05, parallax=None, parallax_amplitude=0.05, parallax_period=150,
                               depth_shadows=False, shadow_threshold=0.2, shadow_min_region=100, drop_depth_shadows=False,
-                              render_view=None, render_size="1280x720", render_point_size=7, render_min_height=None):
+                              render_view=None, render_size="1280x720", render_point_size=7, render_min_height=None,
+                              plan_shapes=False, plan_size="1280x720", plan_point_size=7, plan_stroke=3.0, plan_label_scale=2):
     """Directory loop (reference :153-206), pipelined decode -> GPU -> encode, frame-sharded across ranks.
 
     Every rank writes its own frames' files; each frame has exactly one owner.  resume=True skips
@@ -416,6 +420,12 @@ def batch_generate_depth_maps(input_dir, output_dir, pattern="*.png", downscale_
     else the raw one) made on the device (`depth_pro.render.render_views`: the reference's view presets, `multi` their
     2 x 2 sheet, `plan` the main pipeline's top-down picture, render_min_height its height threshold) at render_size
     ("WxH") with splats of render_point_size pixels, and `{base}_view.json` (the cameras and the counts).
+    plan_shapes=True (implies fit_shapes) writes `{base}_plan.png`, the reference's main picture (pointcloud_pipeline.py's
+    in_memory_pointcloud_visualization): the top-down plan of the cleaned cloud's rows at or above cluster_height, with the
+    fitted rectangles (after the split with split_l_shapes) and circles stroked on it and numbered, all made on the device
+    (`depth_pro.overlay.plan_with_shapes`) at plan_size ("WxH") with splats of plan_point_size pixels, strokes plan_stroke
+    pixels wide and digits of plan_label_scale pixels per font pixel (0: no numbers), and `{base}_plan.json` (parameters,
+    the camera record, the counts).
     """
     params = resolve_stages(**{k: v for k, v in locals().items() if k in _DEFAULTS}, output_dir=output_dir)
     on = [st for st in STAGES if st.name in params]
@@ -710,6 +720,10 @@ def _queue_shapes(frame: dict, p: dict) -> dict:
         rects, n_rects = PC.rectangle_list(table, frame["n_clusters"], MAX_CLUSTERS)
         rows, n_out, info = PC.split_l_shapes(frame["xyz"], frame["labels"], rects, n_rects, frame["count"])
         payload["l_split"] = {"rows": _pinned(rows), "n_out": _pinned(n_out), "info": _pinned(info), "n_rects": _pinned(n_rects)}
+        if p.get("plan"):
+            frame.update(rects=rows, n_rects=n_out)     # on the device, for the plan picture
+    if p.get("plan"):
+        frame["shapes"] = table
     return payload
 
 
@@ -718,7 +732,7 @@ def _write_shapes(base: str, params: dict, out: dict) -> None:
     s, split = out["shapes"], out["shapes"].get("l_split")
     table = s["table"][:min(int(out["cluster"]["n_clusters"]), MAX_CLUSTERS)].numpy()
     p = {key: (None if isinstance(v, float) and v != v else v) for key, v in {**params["cluster"], **params["shapes"]}.items()
-         if key != "l_split"}
+         if key not in ("l_split", "plan")}
     if split is not None:
         summary = PC.shape_summary(table, p, split["rows"][:int(split["n_out"][0])].numpy(),
                                    split["info"][:int(split["n_rects"])].numpy())
@@ -996,6 +1010,30 @@ def _write_views(base: str, params: dict, out: dict) -> None:
                    "counts": RV.stats_dict(r["stats"].numpy(), len(cams))}, f, indent=1)
 
 
+def _queue_planshapes(frame: dict, p: dict) -> dict:
+    """The plan picture with the shapes on it (--plan_shapes), behind the shapes: the plan of the rows the cluster stage
+    fitted, the strokes and numbers from the tables still on the device; then the pinned host copies."""
+    if "rects" not in frame:                            # no split: the reference's rectangle list of the table
+        frame["rects"], frame["n_rects"] = PC.rectangle_list(frame["shapes"], frame["n_clusters"], MAX_CLUSTERS)
+    res = OV.plan_with_shapes(frame["xyz"], frame["cols"], frame["count"], frame["rects"], frame["n_rects"], frame["shapes"],
+                              frame["n_clusters"], size=p["size"], point_size=p["point_size"], min_height=p["min_height"],
+                              stroke=p["stroke"], label_scale=p["label_scale"])
+    return {k: _pinned(res[k]) for k in ("image", "camera", "stats", "plan_stats")}
+
+
+def _write_planshapes(base: str, params: dict, out: dict) -> None:
+    """Writer-thread side (after the frame's event): `{base}_plan.png` (RGB) and `{base}_plan.json`."""
+    r, p = out["planshapes"], params["planshapes"]
+    _write_png(base + "_plan.png", r["image"].numpy())
+    with open(base + "_plan.json", "w") as f:
+        json.dump({"parameters": {"size": list(p["size"]), "point_size": p["point_size"], "min_height": p["min_height"],
+                                  "stroke": p["stroke"], "alpha": OV.STROKE_ALPHA, "label_scale": p["label_scale"],
+                                  "split_l_shapes": p["split"]},
+                   "camera": [None if c != c else float(c) for c in r["camera"].numpy()],
+                   "counts": OV.stats_dict(r["stats"].numpy()),
+                   "plan_counts": RV.stats_dict(r["plan_stats"].numpy(), 1)}, f, indent=1)
+
+
 # ---- each stage's parameter dict from the loop's options `o`, checked first ----
 
 def _ground_params(o: dict) -> dict:
@@ -1017,7 +1055,8 @@ def _cluster_params(o: dict) -> dict:
 
 def _shapes_params(o: dict) -> dict:
     check_circularity(o["circularity_threshold"])
-    return {"circularity_threshold": float(o["circularity_threshold"]), **({"l_split": True} if o["split_l_shapes"] else {})}
+    return {"circularity_threshold": float(o["circularity_threshold"]), **({"l_split": True} if o["split_l_shapes"] else {}),
+            **({"plan": True} if o["plan_shapes"] else {})}    # --plan_shapes: the tables stay in `frame` for that stage
 
 
 def _floor_params(o: dict) -> dict:
@@ -1116,6 +1155,30 @@ def _views_params(o: dict) -> dict:
             "min_height": float(o["render_min_height"]) if plan and o["render_min_height"] is not None else None}
 
 
+def check_plan_shapes(size, point_size, stroke, label_scale) -> Tuple[int, int]:
+    try:
+        w, h = (int(v) for v in str(size).lower().split("x"))
+    except ValueError:
+        raise ValueError(f"--plan_size must be WxH (got {size})") from None
+    if w < 1 or h < 1 or w * h >= 2 ** 31:
+        raise ValueError(f"--plan_size: W and H must be >= 1 and W * H < 2^31 (got {size})")
+    if not (1 <= int(point_size) <= 15 and int(point_size) % 2 == 1):
+        raise ValueError(f"--plan_point_size must be odd and in [1, 15] (got {point_size})")
+    if not (np.isfinite(float(stroke)) and float(stroke) > 0):
+        raise ValueError(f"--plan_stroke must be finite and > 0 (got {stroke})")
+    if not 0 <= int(label_scale) <= 8:
+        raise ValueError(f"--plan_label_scale must be in [0, 8] (got {label_scale})")
+    return w, h
+
+
+def _planshapes_params(o: dict) -> dict:
+    size = check_plan_shapes(o["plan_size"], o["plan_point_size"], o["plan_stroke"], o["plan_label_scale"])
+    height = float(o["cluster_height"])                 # the plan shows the rows the cluster stage fitted
+    return {"size": size, "point_size": int(o["plan_point_size"]), "stroke": float(o["plan_stroke"]),
+            "label_scale": int(o["plan_label_scale"]), "min_height": None if height != height else height,
+            "split": bool(o["split_l_shapes"])}
+
+
 class Stage(NamedTuple):
     """One stage of the frame loop, described once."""
     name: str
@@ -1141,6 +1204,8 @@ STAGES = (
           _queue_cluster, _write_clusters),
     Stage("shapes", "cluster", lambda o: o["fit_shapes"] or o["split_l_shapes"], _shapes_params, ("_shapes.json",),
           _queue_shapes, _write_shapes),
+    Stage("planshapes", "shapes", lambda o: bool(o["plan_shapes"]), _planshapes_params, ("_plan.png", "_plan.json"),
+          _queue_planshapes, _write_planshapes),
     Stage("floor", "clean", lambda o: o["floor_plan"], _floor_params, ("_floorplan.png", "_floorplan.json"),
           _queue_floor, _write_floorplan),
     Stage("slices", "clean", lambda o: bool(o["floor_slices"]), _slices_params, ("_floorslices.txt", "_floorslices.json"),
@@ -1216,7 +1281,7 @@ def main():
                         help="Voxel edge of --mesh_points in metres (default 0.05); normals use radius 2 * voxel_size")
     parser.add_argument("--normals_max_nn", type=int, default=30,
                         help=f"Neighbours at the most per normal (1..{PC.MAX_NN}, default 30)")
-    # the two options below (and --floor_polygons, --floor_slices, --anaglyph, --parallax, --depth_shadows, --render_view and their options) are passed on only when given: a run without them passes the keywords it always passed
+    # the two options below (and --floor_polygons, --floor_slices, --anaglyph, --parallax, --depth_shadows, --render_view, --plan_shapes and their options) are passed on only when given: a run without them passes the keywords it always passed
     parser.add_argument("--simple_mesh", action="store_true", default=argparse.SUPPRESS,
                         help="Mesh the voxels of --mesh_points (which it implies) as the reference's --mesh_method simple "
                              "does: nearest neighbours, a fan of triangles, clean-up; {frame}_mesh.ply and {frame}_mesh.json")
@@ -1276,6 +1341,18 @@ def main():
                         help="Side of a point's square in pixels for --render_view, odd, 1..15 (default 7)")
     parser.add_argument("--render_min_height", type=float, default=argparse.SUPPRESS,
                         help="Show only the points with y >= this height in --render_view plan (default: all)")
+    parser.add_argument("--plan_shapes", action="store_true", default=argparse.SUPPRESS,
+                        help="Write {frame}_plan.png, the top-down plan of the cleaned cloud with the fitted rectangles and circles "
+                             "stroked on it and numbered, made on the GPU (implies --fit_shapes), and {frame}_plan.json (parameters, "
+                             "camera, counts)")
+    parser.add_argument("--plan_size", type=str, default=argparse.SUPPRESS, metavar="WxH",
+                        help="Size of the picture of --plan_shapes (default 1280x720)")
+    parser.add_argument("--plan_point_size", type=int, default=argparse.SUPPRESS,
+                        help="Side of a point's square in pixels for --plan_shapes, odd, 1..15 (default 7)")
+    parser.add_argument("--plan_stroke", type=float, default=argparse.SUPPRESS,
+                        help="Width of the shapes' outlines in pixels for --plan_shapes (default 3.0)")
+    parser.add_argument("--plan_label_scale", type=int, default=argparse.SUPPRESS,
+                        help="Pixels per font pixel of the shapes' numbers for --plan_shapes, 0..8 (default 2; 0: no numbers)")
     parser.add_argument("--boundary_dir", type=str, default=None,
                         help="Score each frame against DIR/{frame}.npy with the Depth Pro boundary metric (float32: a depth, "
                              "SI_boundary_F1; bool / uint8: a mask, SI_boundary_Recall); writes {frame}_boundary.json")
@@ -1287,7 +1364,8 @@ def main():
                              "_floorplan_polygons.json; with --floor_slices: and {frame}_floorslices.txt / .json; with "
                              "--boundary_dir, for a frame with a target: and {frame}_boundary.json; with --anaglyph: and "
                              "{frame}_anaglyph.png; with --parallax: and {frame}_parallax.png; with --depth_shadows: and {frame}_shadows.png / "
-                             ".json; with --render_view: and {frame}_view.png / .json) already exists in --output_dir")
+                             ".json; with --render_view: and {frame}_view.png / .json; with --plan_shapes: and {frame}_plan.png / .json) already "
+                             "exists in --output_dir")
     parser.add_argument("--colormap", type=str, default="turbo",
                         choices=["turbo", "viridis", "plasma", "inferno", "magma", "cividis", "jet"],
                         help="Colormap for depth visualization")

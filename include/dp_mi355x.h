@@ -293,6 +293,20 @@ int dp_gemm(const dp_gemm_args* args, dp_stream_t stream);
  * (the 256 x 128 big engine; the tile hint is ignored).  Replaces the image encoder's and the FOV
  * encoder's ViT Linears / patch embeds -- two ViT-L with their own weights over the same x2 input
  * (encoder.py:308-311, fov.py:66-72) -- run side by side as one workgroup range per problem.
+ *
+ * Folded LayerNorm with groups >= 2 (additive; ABI 20): two forms of the ln_* fields, with
+ * ln_part_out / ln_xb_out / ln_part_in / ln_colsum per problem (all problems set the same ones) and
+ * the meaning they have in dp_gemm_args:
+ *   producer (the side proj / fc2): ln_part_out and ln_xb_out both, C fp32 and accumulated into,
+ *     act NONE, N % 128 == 0, no R1 / R2 / pos / row_group.  C is what the launch without ln_*
+ *     writes, bit for bit; ln_xb_out[m][ldc] = those fp32 values rounded to dtype;
+ *     ln_part_out[m][N/128][2] = (mean, M2) of each 128-column chunk of them.
+ *   consumer (the side qkv / fc1): ln_part_in and ln_colsum both, K == 1024, a 16-bit C with
+ *     ldc % 8 == 0, act NONE or GELU, no gamma (a per-column scale is folded into B / bias /
+ *     ln_colsum), ln_eps > 0 and equal in every problem, no accumulate / R1 / R2 / pos / row_group:
+ *     v = rstd * acc - rstd * mean * ln_colsum[n] + bias[n], then act.
+ * Any other ln_* field or combination in a grouped call (ln_xl, ln_rs_out, ln_rs_in, K != 1024 for
+ * a consumer, N % 128 != 0 for a producer, ...) is DP_ERR_ARG.  groups == 1 is dp_gemm, with its rules.
  */
 int dp_gemm_grouped(const dp_gemm_args* args, int32_t groups, dp_stream_t stream);
 

@@ -493,8 +493,8 @@ extern "C" int dp_gemm(const dp_gemm_args* a, dp_stream_t stream) {
 
 // Same-shape problems that differ only in their operand pointers, one launch (the image and FOV
 // encoders' ViT GEMMs: encoder.py:308-311 and fov.py:66-72 run two ViT-L on the same x2 input).
-// Always the 256 x 128 big engine (the tile hint is ignored): the side encoders' M = 577 plans
-// onto it anyway.
+// Always the grouped 128 x 128 big tile (the tile hint is ignored), which also has the two folded-LN
+// forms of a grouped launch (dp_mi355x.h): checked below, not by gemm_plan.
 extern "C" int dp_gemm_grouped(const dp_gemm_args* a, int32_t groups, dp_stream_t stream) {
   if (!a || groups < 1 || groups > DP_MAX_GROUPS) return DP_ERR_ARG;
   if (groups == 1) return dp_gemm(a, stream);
@@ -502,9 +502,25 @@ extern "C" int dp_gemm_grouped(const dp_gemm_args* a, int32_t groups, dp_stream_
   for (int g = 0; g < groups; ++g) {
     GemmP q;
     int t = 0;
-    const int rc = gemm_plan(&a[g], q, t);
-    if (rc) return rc;
+    // The folded-LN forms of a grouped launch (the 128 x 128 tile's own epilogues, dp_mi355x.h) are
+    // checked here: the problem is planned without its ln_* fields (gemm_plan knows them for the
+    // 8-phase engines only), which then go into the launch per group.
+    dp_gemm_args plain = a[g];
+    plain.ln_part_out = nullptr; plain.ln_xb_out = nullptr; plain.ln_part_in = nullptr; plain.ln_colsum = nullptr;
     const dp_gemm_args &x = a[0], &y = a[g];
+    const bool lnp = y.ln_part_out || y.ln_xb_out, lnc = y.ln_part_in || y.ln_colsum;
+    const int rc = gemm_plan(&plain, q, t);
+    if (rc) return rc;
+    if (lnp && (lnc || !y.ln_part_out || !y.ln_xb_out || !y.accumulate || y.c_dtype != DP_F32 || y.act != DP_ACT_NONE ||
+                y.N % 128 != 0 || y.R1 || y.R2 || y.pos || y.row_group))
+      return DP_ERR_ARG;
+    if (lnc && (!y.ln_part_in || !y.ln_colsum || y.K != 1024 || y.accumulate || y.c_dtype == DP_F32 || y.gamma ||
+                (y.act != DP_ACT_NONE && y.act != DP_ACT_GELU) || !(y.ln_eps > 0.f) || y.ldc % 8 != 0 || y.R1 || y.R2 ||
+                y.pos || y.row_group))
+      return DP_ERR_ARG;
+    if (!y.ln_part_out != !x.ln_part_out || !y.ln_xb_out != !x.ln_xb_out || !y.ln_part_in != !x.ln_part_in ||
+        !y.ln_colsum != !x.ln_colsum || ((lnc) && y.ln_eps != x.ln_eps))
+      return DP_ERR_ARG;
     // everything but the operand pointers must agree
     if (y.M != x.M || y.N != x.N || y.K != x.K || y.dtype != x.dtype || y.lda != x.lda || y.ldb != x.ldb ||
         y.a_mode != DP_A_DENSE || x.a_mode != DP_A_DENSE || y.relu_a || y.act != x.act ||
@@ -513,12 +529,14 @@ extern "C" int dp_gemm_grouped(const dp_gemm_args* a, int32_t groups, dp_stream_
         !y.R2 != !x.R2 || y.ldr2 != x.ldr2 || y.ldc != x.ldc || y.c_dtype != x.c_dtype ||
         y.accumulate != x.accumulate || y.store_mode != DP_STORE_ROWS || x.store_mode != DP_STORE_ROWS ||
         y.row_group != x.row_group || y.row_group_out != x.row_group_out || y.row_off != x.row_off ||
-        y.head_w || y.head_corr || y.N % 8 != 0 || y.ln_part_out || y.ln_xb_out || y.ln_xl || y.ln_part_in ||
-        y.ln_rs_out || y.ln_rs_in ||
-        y.ln_colsum)
+        y.head_w || y.head_corr || y.N % 8 != 0 || y.ln_xl || y.ln_rs_out || y.ln_rs_in)
       return DP_ERR_ARG;
-    if (g == 0) p = q;
-    p.grp[g] = GemmP::Group{q.A, q.B, q.bias, q.gamma, q.pos, q.R1, q.R2, q.C};
+    if (g == 0) {
+      p = q;
+      p.ln_eps = y.ln_eps;
+    }
+    p.grp[g] = GemmP::Group{q.A, q.B, q.bias, q.gamma, q.pos, q.R1, q.R2, q.C,
+                            y.ln_part_out, (u16*)y.ln_xb_out, y.ln_part_in, y.ln_colsum};
   }
   p.groups = groups;
   hipStream_t s = (hipStream_t)stream;

@@ -10,13 +10,15 @@
 
 #include "dp_gemm_dev.h"
 #include "dp_gemm_epilogue.h"
+#include "dp_ln_merge.h"
 
 namespace {
 
 // NW = waves per workgroup: 8 (one workgroup per CU), or 4 (two workgroups per CU, each
 // wave one per SIMD: one workgroup's epilogue runs beside the other's K loop).
 // EACT: -1 = the general epilogue (runtime operand set); DP_ACT_* = the load-free MFMA-layout
-// epilogue with that activation (epilogue_mfma; fast_epi_act decides on the host).
+// epilogue with that activation (epilogue_mfma; fast_epi_act decides on the host); EPI_ACC + act:
+// epilogue_acc32; EPI_LNP / EPI_LNC + act: the grouped 128 x 128 folded-LayerNorm producer / consumer.
 // GRP: a dp_gemm_grouped launch -- the workgroup's problem (wgid / tiles per problem) supplies the
 // operand pointers.
 template <typename K_, int BM, int BN, int BKT, int NS, bool PIPE, bool CONV, bool RELU, int NW = 8, int EACT = -1,
@@ -60,6 +62,8 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) gemm_big_kernel(cons
     const GemmP::Group& q = p_arg.grp[g];
     p_grp.A = q.A; p_grp.B = q.B; p_grp.bias = q.bias; p_grp.gamma = q.gamma; p_grp.pos = q.pos;
     p_grp.R1 = q.R1; p_grp.R2 = q.R2; p_grp.C = q.C;
+    p_grp.ln_part_out = q.ln_part_out; p_grp.ln_xb_out = q.ln_xb_out;
+    p_grp.ln_part_in = q.ln_part_in; p_grp.ln_colsum = q.ln_colsum;
   }
   // split-K: this workgroup's K-step range and its fp32 partial slab as a plain C (no epilogue
   // operands: the reduce launch applies them to the sum)
@@ -83,6 +87,19 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) gemm_big_kernel(cons
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   DP_STAMPS_DECL;
   DP_STAMP(st0_);
+  // folded-LN consumer (EPI_LNC): thread r < BM asks for tile row r's 8 chunk statistics now (16
+  // VGPRs over the K loop, older than every LDS-DMA piece, so the counted waits cover them) and
+  // merges them after the loop -- no load latency in the epilogue
+  constexpr bool LNP = EACT == EPI_LNP, LNC = EACT >= EPI_LNC;
+  static_assert(!(LNP || LNC) || (GRP && BM == 128 && BN == 128 && NW == 8), "folded LN: the grouped 128 x 128 tile");
+  f32x4_t lnc_part[4];
+  if constexpr (LNC) {
+    if (tid < BM) {
+      const f32x4_t* pp = (const f32x4_t*)(p.ln_part_in + (long long)min(m0 + tid, p.M - 1) * 16);
+      #pragma unroll
+      for (int i = 0; i < 4; ++i) lnc_part[i] = pp[i];
+    }
+  }
 
   // LDS-DMA piece i of this thread covers tile row i*ROWS_PER_ROUND + wave*ROWS_PER_WAVE_PIECE + lane/CR;
   // LDS slot lane%CR of that row holds logical chunk (lane%CR) ^ swz(row): the swizzle is
@@ -290,7 +307,31 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) gemm_big_kernel(cons
       for (int j = 0; j < FN; ++j) asm volatile("" ::"v"(acc[i][j][0]), "v"(acc[i][j][1]), "v"(acc[i][j][2]), "v"(acc[i][j][3]));
     return;
   }
-  if constexpr (EACT >= EPI_ACC) {
+  if constexpr (LNC) {
+    // folded-LN consumer: the tile rows' (rstd, -rstd * mean), merged once per workgroup (table
+    // beside the ring), then epilogue_mfma with them
+    __shared__ float2 ln_rs_s[BM];
+    if (tid < BM) ln_rs_s[tid] = ln_merge_row(lnc_part, p.ln_eps);
+    lds_barrier();  // the ring is free once every wave has left the K loop; the table is written
+    constexpr int PF = (FM * 16 * TN * 2 * NW <= SMEM) ? FM : FM / 2;
+    epilogue_mfma<K_, EACT - EPI_LNC, FM, FN, TN, PF, true>(p, acc, smem + wave * (PF * 16 * TN * 2), lane,
+                                                             m0 + wm * TM, n0 + wn * TN, ln_rs_s + wm * TM);
+    return;
+  } else if constexpr (LNP) {
+    // folded-LN producer: every wave leaves its rows' 32-column sums in the table (beside the
+    // ring: no barrier before), then thread r merges tile row r's four into part[m][chunk n0 / 128]
+    static_assert(WN == 4 && TN == 32, "one 128-column chunk over 4 waves");
+    __shared__ f32x4_t ln_st[BM * 4];
+    epilogue_acc32_ln<K_, FM, FN>(p, acc, ln_st + wm * TM * 4 + wn, lane, m0 + wm * TM, n0 + wn * TN);
+    lds_barrier();
+    if (tid < BM && m0 + tid < p.M) {
+      f32x4_t e[4];
+      #pragma unroll
+      for (int w = 0; w < 4; ++w) e[w] = ln_st[tid * 4 + w];
+      *(float2*)(p.ln_part_out + ((long long)(m0 + tid) * (p.N / 128) + n0 / 128) * 2) = ln_chunk_merge(e);
+    }
+    return;
+  } else if constexpr (EACT >= EPI_ACC) {
     epilogue_acc32<EACT - EPI_ACC, FM, FN>(p, acc, lane, m0 + wm * TM, n0 + wn * TN);
     return;
   } else if constexpr (EACT >= 0) {
@@ -369,7 +410,17 @@ int launch_big(const GemmP& p0, bool conv, hipStream_t s) {
       if (conv || p.relu_a) return DP_ERR_ARG;
       dim3 g(p.tiles_n * p.tiles_m * p.groups);
 #define DP_GRP(E_) hipLaunchKernelGGL((gemm_big_kernel<K_, BM, BN, 64, 3, true, false, false, 8, E_, true>), g, dim3(NT_BIG), 0, s, p)
-      if (ea == DP_ACT_NONE) DP_GRP(DP_ACT_NONE);
+      // the folded-LN forms (dp_gemm_grouped checked them): the 128 x 128 tile's own epilogues
+      const bool lnp = p.grp[0].ln_part_out, lnc = p.grp[0].ln_part_in;
+      if constexpr (BM == 128) {
+        if (lnp) DP_GRP(EPI_LNP);
+        else if (lnc && p.act == DP_ACT_GELU) DP_GRP(EPI_LNC + DP_ACT_GELU);
+        else if (lnc) DP_GRP(EPI_LNC + DP_ACT_NONE);
+      } else if (lnp || lnc) {
+        return DP_ERR_ARG;
+      }
+      if (lnp || lnc) { /* launched above */ }
+      else if (ea == DP_ACT_NONE) DP_GRP(DP_ACT_NONE);
       else if (ea == DP_ACT_GELU) DP_GRP(DP_ACT_GELU);
       else if (ea == EPI_ACC) DP_GRP(EPI_ACC);
       else DP_GRP(-1);

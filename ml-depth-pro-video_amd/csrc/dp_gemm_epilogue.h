@@ -6,6 +6,7 @@
 //   epilogue_mfma   load-free, in the MFMA register layout (16-bit C, no per-row operand): the
 //                   big, 8-phase and 8-phase 320 x 256 engines
 //   epilogue_acc32  fp32 C accumulated into, MFMA layout: the big engine
+//   epilogue_acc32_ln  ... + the folded-LayerNorm producer outputs (grouped 128 x 128 launches)
 //   head_ps_rows    the composed depth-head tail (DP_STORE_HEAD_PS): the big engine
 // An engine's private epilogue lives beside its kernel.
 
@@ -181,20 +182,26 @@ __device__ __forceinline__ void epilogue_rows(const GemmP& p, const ColConst& cc
 // segments (TN * 2 bytes per row, 16 B per lane).  PF fragment rows per pass (slab: PF * 16 *
 // TN * 2 bytes per wave).  LDS operations of one wave complete in order, so the write -> read
 // -> next pass's write sequence needs no barrier (the slab is the wave's own).
-template <typename K_, int ACT, int FM, int FN, int TN, int PF>
+// LNC: the consumer of a folded LayerNorm (grouped 128 x 128 launches, dp_gemm_args.ln_part_in): per
+// value rstd * acc - rstd * mean * colsum[n] + bias[n], then ACT (no gamma) -- the arithmetic of the
+// 8-phase 320 x 256 engine's epilogue_mfma_lnc; `rsm` = (rstd, -rstd * mean) of the wave's rows in
+// LDS, merged once per workgroup by the kernel.
+template <typename K_, int ACT, int FM, int FN, int TN, int PF, bool LNC = false>
 __device__ __forceinline__ void epilogue_mfma(const GemmP& p, f32x4_t (&acc)[FM][FN], char* slab, int lane,
-                                              int m_base, int n_base) {
+                                              int m_base, int n_base, const float2* rsm = nullptr) {
   constexpr int CH = TN / 8;            // 16-B chunks per staged row
   constexpr int RPI = 64 / CH;          // rows per read-back instruction
   static_assert(FM % PF == 0 && (CH == 16 || CH == 8 || CH == 4), "tile");
   const int t = lane & 15, g = lane >> 4;
-  float bias[FN][4], gam[FN][4];
+  float bias[FN][4], gam[FN][4];        // (LNC: gam = the column sums of B)
   #pragma unroll
   for (int fn = 0; fn < FN; ++fn) {
     const int n = n_base + fn * 16 + 4 * g;
     const bool ok = n < p.N;
     const float4 b = (p.bias && ok) ? *(const float4*)(p.bias + n) : make_float4(0.f, 0.f, 0.f, 0.f);
-    const float4 q = (p.gamma && ok) ? *(const float4*)(p.gamma + n) : make_float4(1.f, 1.f, 1.f, 1.f);
+    float4 q;
+    if constexpr (LNC) q = ok ? *(const float4*)(p.ln_colsum + n) : make_float4(0.f, 0.f, 0.f, 0.f);
+    else q = (p.gamma && ok) ? *(const float4*)(p.gamma + n) : make_float4(1.f, 1.f, 1.f, 1.f);
     bias[fn][0] = b.x; bias[fn][1] = b.y; bias[fn][2] = b.z; bias[fn][3] = b.w;
     gam[fn][0] = q.x; gam[fn][1] = q.y; gam[fn][2] = q.z; gam[fn][3] = q.w;
   }
@@ -205,14 +212,23 @@ __device__ __forceinline__ void epilogue_mfma(const GemmP& p, f32x4_t (&acc)[FM]
       #pragma unroll
       for (int fn = 0; fn < FN; ++fn) {
         // packed-f32 arithmetic on the lane's 4 columns (gelu_erf4): same values as per element
-        f32x4_t x = acc[f0 + fm][fn] + f32x4_t{bias[fn][0], bias[fn][1], bias[fn][2], bias[fn][3]};
+        f32x4_t x;
+        if constexpr (LNC) {
+          const float2 rs = rsm[(f0 + fm) * 16 + t];
+          x = __builtin_elementwise_fma(
+              acc[f0 + fm][fn], (f32x4_t)(rs.x),
+              __builtin_elementwise_fma(f32x4_t{gam[fn][0], gam[fn][1], gam[fn][2], gam[fn][3]}, (f32x4_t)(rs.y),
+                                        f32x4_t{bias[fn][0], bias[fn][1], bias[fn][2], bias[fn][3]}));
+        } else {
+          x = acc[f0 + fm][fn] + f32x4_t{bias[fn][0], bias[fn][1], bias[fn][2], bias[fn][3]};
+        }
         if constexpr (ACT == DP_ACT_RELU) {
           #pragma unroll
           for (int r = 0; r < 4; ++r) x[r] = fmaxf(x[r], 0.f);
         } else if constexpr (ACT == DP_ACT_GELU) {
           x = gelu_erf4(x);
         }
-        x = x * f32x4_t{gam[fn][0], gam[fn][1], gam[fn][2], gam[fn][3]};
+        if constexpr (!LNC) x = x * f32x4_t{gam[fn][0], gam[fn][1], gam[fn][2], gam[fn][3]};
         const int row = fm * 16 + t;
         const int chunk = fn * 2 + (g >> 1);
         uint2 w;
@@ -277,6 +293,86 @@ __device__ __forceinline__ void epilogue_acc32(const GemmP& p, f32x4_t (&acc)[FM
       }
       if (m < p.M) *(f32x4_t*)(C + (long long)m * p.ldc + n_base + fn * 16 + 4 * g) = x;
     }
+    #pragma unroll
+    for (int fn = 0; fn < FN; ++fn) cur[fn] = nxt[fn];
+  }
+}
+
+// epilogue_acc32 (ACT none) + the producer side of a folded LayerNorm, for the grouped 128 x 128
+// launches (the side encoders' proj / fc2): besides C (fp32, accumulated, bit-identical to
+// epilogue_acc32) every new row goes out in 16 bits (p.ln_xb_out, 8 B per lane) and leaves the
+// statistics of the wave's TN = 32 columns in LDS, shifted as in the 320 x 256 producer (shift = the
+// row's first value in the wave, so a large common offset cancels exactly) but in two passes over
+// the lane's 8 registers: (shift, mean - shift, M2) at st[4 * wave row] (`st` = the wave's column of
+// the workgroup's [tile row][wn] table).  The
+// tile is one 128-column chunk wide, so the kernel merges a row's WN entries into its (mean, M2)
+// after a barrier (ln_chunk_merge): no hand-off between workgroups.  Whole column tiles only.
+template <typename K_, int FM, int FN>
+__device__ __forceinline__ void epilogue_acc32_ln(const GemmP& p, f32x4_t (&acc)[FM][FN], f32x4_t* st, int lane,
+                                                  int m_base, int n_base) {
+  #pragma clang fp contract(off)
+  const int t = lane & 15, g = lane >> 4;
+  float bias[FN][4], gam[FN][4];
+  #pragma unroll
+  for (int fn = 0; fn < FN; ++fn) {
+    const int n = n_base + fn * 16 + 4 * g;
+    const float4 b = p.bias ? *(const float4*)(p.bias + n) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 q = p.gamma ? *(const float4*)(p.gamma + n) : make_float4(1.f, 1.f, 1.f, 1.f);
+    bias[fn][0] = b.x; bias[fn][1] = b.y; bias[fn][2] = b.z; bias[fn][3] = b.w;
+    gam[fn][0] = q.x; gam[fn][1] = q.y; gam[fn][2] = q.z; gam[fn][3] = q.w;
+  }
+  float* const C = (float*)p.C;
+  f32x4_t cur[FN], nxt[FN];
+  auto load_row = [&](int fm, f32x4_t (&c)[FN]) __attribute__((always_inline)) {
+    const int m = min(m_base + fm * 16 + t, p.M - 1);
+    #pragma unroll
+    for (int fn = 0; fn < FN; ++fn) c[fn] = *(const f32x4_t*)(C + (long long)m * p.ldc + n_base + fn * 16 + 4 * g);
+  };
+  load_row(0, cur);
+  #pragma unroll
+  for (int fm = 0; fm < FM; ++fm) {
+    if (fm + 1 < FM) load_row(fm + 1, nxt);
+    const int m = m_base + fm * 16 + t;
+    f32x4_t x[FN];
+    #pragma unroll
+    for (int fn = 0; fn < FN; ++fn) {
+      #pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float v = acc[fm][fn][r] + bias[fn][r];
+        x[fn][r] = v * gam[fn][r] + cur[fn][r];
+      }
+      if (m < p.M) {
+        *(f32x4_t*)(C + (long long)m * p.ldc + n_base + fn * 16 + 4 * g) = x[fn];
+        uint2 w;
+        w.x = K_::pack2(x[fn][0], x[fn][1]);
+        w.y = K_::pack2(x[fn][2], x[fn][3]);
+        *(uint2*)(p.ln_xb_out + (long long)m * p.ldc + n_base + fn * 16 + 4 * g) = w;
+      }
+    }
+    const float sh = __shfl(x[0][0], t);    // the row's value at column n_base (lane t, g = 0)
+    float d[FN][4], s1 = 0.f;
+    #pragma unroll
+    for (int fn = 0; fn < FN; ++fn)
+      #pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        d[fn][r] = x[fn][r] - sh;
+        s1 += d[fn][r];
+      }
+    // the row's TN columns: 4 lanes (g)
+    s1 += __shfl_xor(s1, 16);
+    s1 += __shfl_xor(s1, 32);
+    const float dm = s1 * (1.f / 32);
+    float s2 = 0.f;
+    #pragma unroll
+    for (int fn = 0; fn < FN; ++fn)
+      #pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float e = d[fn][r] - dm;
+        s2 += e * e;
+      }
+    s2 += __shfl_xor(s2, 16);
+    s2 += __shfl_xor(s2, 32);
+    if (g == 0) st[(fm * 16 + t) * 4] = f32x4_t{sh, dm, s2, 0.f};
     #pragma unroll
     for (int fn = 0; fn < FN; ++fn) cur[fn] = nxt[fn];
   }

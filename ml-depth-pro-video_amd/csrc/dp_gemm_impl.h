@@ -100,6 +100,11 @@ struct GemmP {
     const u16* R1;
     const u16* R2;
     void* C;
+    // the grouped folded-LN forms (dp_gemm_grouped): producer outputs / consumer inputs of problem g
+    float* ln_part_out;
+    u16* ln_xb_out;
+    const float* ln_part_in;
+    const float* ln_colsum;
   } grp[DP_MAX_GROUPS];
 };
 
@@ -233,8 +238,12 @@ __host__ __device__ inline bool needs_rowld(const GemmP& p) {
 
 // EACT of the engine variants: the compile-time epilogue.  -1: the general, runtime one;
 // DP_ACT_*: epilogue_mfma (no per-row operand, 16-bit C); EPI_ACC + DP_ACT_*: epilogue_acc32
-// (fp32 C accumulated into, no other per-row operand).
+// (fp32 C accumulated into, no other per-row operand); EPI_LNP / EPI_LNC + DP_ACT_*: below.
 constexpr int EPI_ACC = 16;
+// the grouped 128 x 128 launches' folded-LN epilogues (dp_gemm_big.h): EPI_LNP = the producer
+// (epilogue_acc32 + 16-bit rows + chunk statistics), EPI_LNC + DP_ACT_* = the consumer (epilogue_mfma
+// with the rows' mean / rstd applied)
+constexpr int EPI_LNP = 32, EPI_LNC = 48;
 __host__ inline int fast_epi_act(const GemmP& p) {
   if (p.dbg & DBG_NO_FAST_EPILOGUE) return -1;
   if (!needs_rowld(p)) return p.c_dtype == DP_F32 ? -1 : p.act;

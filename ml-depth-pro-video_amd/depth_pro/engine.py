@@ -40,6 +40,12 @@ def ln_fold_enabled() -> bool:
     return not ({"ln", "vitgemm"} & _ABLATE)
 
 
+def side_ln_fold_enabled() -> bool:
+    """The same for the grouped image + FOV encoders (dp_gemm_grouped's folded-LN forms): also off
+    under 'sideln', which drops exactly their standalone LayerNorm launches."""
+    return ln_fold_enabled() and "sideln" not in _ABLATE
+
+
 NWIN = 35
 TOK = TOKENS            # 577
 PTOK = TOKENS - 1       # 576
@@ -148,6 +154,50 @@ def precision_codes(codes) -> Tuple[int, int]:
     return v, d
 
 
+def pack_vit(sd: Dict[str, torch.Tensor], vit: str, device: torch.device, vdt, blocks=None) -> Dict[str, object]:
+    """One ViT's share of `pack_weights` (prefix `vit`; `blocks`: only these Blocks, for tests).
+
+    With its LayerNorms folded (`ln_fold_enabled` for the patch encoder, `side_ln_fold_enabled`
+    for the image / FOV encoders) a ViT reads only the folded qkv / fc1 (ops.fold_layernorm): the
+    unfolded ones (350 MB of 16-bit weights per ViT) are not packed, and for the side
+    encoders neither are norm1 / norm2 -- one weight set per LayerNorm path."""
+    g = lambda k: sd[k].detach().to(device)  # noqa: E731
+    P: Dict[str, object] = {}
+    side = vit != "encoder.patch_encoder."
+    folded = side_ln_fold_enabled() if side else ln_fold_enabled()
+    blocks = range(DEPTH) if blocks is None else blocks
+    P[vit + "cls"] = _f32(g(vit + "cls_token")).reshape(D)
+    P[vit + "pos"] = _f32(g(vit + "pos_embed")).reshape(TOK, D)
+    P[vit + "pe.w"] = g(vit + "patch_embed.proj.weight").reshape(D, -1).to(vdt).contiguous()
+    P[vit + "pe.b"] = _f32(g(vit + "patch_embed.proj.bias"))
+    for i in blocks:
+        b = f"{vit}blocks.{i}."
+        for n in ("norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias", "attn.qkv.bias",
+                  "attn.proj.bias", "mlp.fc1.bias", "mlp.fc2.bias", "ls1.gamma", "ls2.gamma"):
+            if folded and side and n.startswith("norm"):
+                continue
+            P[b + n] = _f32(g(b + n))
+        for n in ("attn.qkv.weight", "attn.proj.weight", "mlp.fc1.weight", "mlp.fc2.weight"):
+            if folded and n in ("attn.qkv.weight", "mlp.fc1.weight"):
+                continue
+            P[b + n] = g(b + n).to(vdt).contiguous()
+    P[vit + "norm.weight"] = _f32(g(vit + "norm.weight"))
+    P[vit + "norm.bias"] = _f32(g(vit + "norm.bias"))
+    if folded:
+        # norm1 / norm2 folded into the qkv / fc1 that consume them (ops.fold_layernorm): the
+        # residual GEMMs hand the next Linear 16-bit rows + chunk statistics instead of a LayerNorm
+        # pass (Engine._vit_steps, DESIGN.md 3); the qkv's log2q gamma rides in the folded weights
+        qg = ops.log2q_gamma(HEADS, D // HEADS, device)
+        for i in blocks:
+            b = f"{vit}blocks.{i}."
+            for lin, ln, cs in (("attn.qkv", "norm1", qg), ("mlp.fc1", "norm2", None)):
+                wf, bf, sf = ops.fold_layernorm(g(b + lin + ".weight").float(), g(b + lin + ".bias").float(),
+                                                g(b + ln + ".weight").float(), g(b + ln + ".bias").float(),
+                                                vdt, cs)
+                P[b + lin + ".fold.w"], P[b + lin + ".fold.b"], P[b + lin + ".fold.s"] = wf, bf, sf
+    return P
+
+
 def pack_weights(sd: Dict[str, torch.Tensor], device: torch.device, dtype_code) -> Dict[str, object]:
     """Convert a (reference-named) state dict into GEMM-ready device tensors.
 
@@ -165,41 +215,9 @@ def pack_weights(sd: Dict[str, torch.Tensor], device: torch.device, dtype_code) 
     vdt, dt = ops.torch_dtype(vcode), ops.torch_dtype(dcode)
     g = lambda k: sd[k].detach().to(device)  # noqa: E731
     P: Dict[str, object] = {}
-    fold = ln_fold_enabled()
     for vit in ("encoder.patch_encoder.", "encoder.image_encoder.", "fov.encoder.0."):
-        if vit + "cls_token" not in sd:
-            continue
-        # the patch encoder with its LayerNorms folded reads only the folded qkv / fc1 (below): the
-        # unfolded ones (350 MB of 16-bit weights) are not packed
-        folded = fold and vit == "encoder.patch_encoder."
-        P[vit + "cls"] = _f32(g(vit + "cls_token")).reshape(D)
-        P[vit + "pos"] = _f32(g(vit + "pos_embed")).reshape(TOK, D)
-        P[vit + "pe.w"] = g(vit + "patch_embed.proj.weight").reshape(D, -1).to(vdt).contiguous()
-        P[vit + "pe.b"] = _f32(g(vit + "patch_embed.proj.bias"))
-        for i in range(DEPTH):
-            b = f"{vit}blocks.{i}."
-            for n in ("norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias", "attn.qkv.bias",
-                      "attn.proj.bias", "mlp.fc1.bias", "mlp.fc2.bias", "ls1.gamma", "ls2.gamma"):
-                P[b + n] = _f32(g(b + n))
-            for n in ("attn.qkv.weight", "attn.proj.weight", "mlp.fc1.weight", "mlp.fc2.weight"):
-                if folded and n in ("attn.qkv.weight", "mlp.fc1.weight"):
-                    continue
-                P[b + n] = g(b + n).to(vdt).contiguous()
-        P[vit + "norm.weight"] = _f32(g(vit + "norm.weight"))
-        P[vit + "norm.bias"] = _f32(g(vit + "norm.bias"))
-        if folded:
-            # norm1 / norm2 folded into the qkv / fc1 that consume them (ops.fold_layernorm): the
-            # patch encoder's residual GEMMs hand the next Linear 16-bit rows + chunk statistics
-            # instead of a LayerNorm pass (Engine._vit); the qkv's log2q gamma rides
-            # in the folded weights
-            qg = ops.log2q_gamma(HEADS, D // HEADS, device)
-            for i in range(DEPTH):
-                b = f"{vit}blocks.{i}."
-                for lin, ln, cs in (("attn.qkv", "norm1", qg), ("mlp.fc1", "norm2", None)):
-                    wf, bf, sf = ops.fold_layernorm(g(b + lin + ".weight").float(), g(b + lin + ".bias").float(),
-                                                    g(b + ln + ".weight").float(), g(b + ln + ".bias").float(),
-                                                    vdt, cs)
-                    P[b + lin + ".fold.w"], P[b + lin + ".fold.b"], P[b + lin + ".fold.s"] = wf, bf, sf
+        if vit + "cls_token" in sd:
+            P.update(pack_vit(sd, vit, device, vdt))
     # encoder project / upsample
     for name, n_up in (("upsample_latent0", 3), ("upsample_latent1", 2), ("upsample0", 1),
                        ("upsample1", 1), ("upsample2", 1)):
@@ -256,11 +274,12 @@ def pack_weights(sd: Dict[str, torch.Tensor], device: torch.device, dtype_code) 
 
 # ---------------------------------------------------------------------- engine
 class _ViTBuffers:
-    def __init__(self, rows: int, dt, dev, out_dt=None, ln_fold: bool = False):
+    def __init__(self, rows: int, dt, dev, out_dt=None, ln_fold: bool = False, part: bool = False):
         self.rows = rows
         self.x = torch.empty(rows, D, dtype=torch.float32, device=dev)
-        # folded LayerNorm: (mean, M2) of each 128-column chunk of the rows in `h` (un-normalised)
-        self.part = torch.empty(rows, D // 128, 2, dtype=torch.float32, device=dev) if ln_fold else None
+        # folded LayerNorm: (mean, M2) of each 128-column chunk of the rows in `h` (un-normalised);
+        # `part` alone: the side encoders' fold, whose residual stream stays fp32 in `x`
+        self.part = torch.empty(rows, D // 128, 2, dtype=torch.float32, device=dev) if ln_fold or part else None
         self.h = torch.empty(rows, D, dtype=dt, device=dev)
         # folded path: the residual stream between blocks is split, x = h (16 bits) + an 8-bit low
         # part xl (steps of ulp(h) / 256; the proj / fc2 epilogues read and update both, dp_gemm's
@@ -269,7 +288,8 @@ class _ViTBuffers:
         self.xl = torch.empty(rows, D, dtype=torch.int8, device=dev) if ln_fold else None
         # (ABI 13): every row's (rstd, -rstd * mean), merged by the proj / fc2 producers' last
         # workgroup per row tile for the qkv / fc1 consumers on the persistent engine; padded to whole
-        # 256-row tiles, the rows the consumer's constant-slot DMA reads
+        # 256-row tiles, which is more than needed: the consumer clamps rows past M to the pair holding
+        # row M - 1, so dp_gemm asks only for M rounded up to an even row count
         self.rs = (torch.empty((rows + 255) // 256 * 256, 2, dtype=torch.float32, device=dev)
                    if ln_fold else None)
         self.qkv = torch.empty(rows, 3 * D, dtype=dt, device=dev)
@@ -399,7 +419,7 @@ class Engine:
         if device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
         self.vcode, self.code = precision_codes(dtype_code)
-        if packed[next(k for k in packed if k.endswith("attn.qkv.weight"))].dtype != ops.torch_dtype(self.vcode) \
+        if packed[next(k for k in packed if k.endswith("attn.proj.weight"))].dtype != ops.torch_dtype(self.vcode) \
                 or packed["decoder.convs.4"].dtype != ops.torch_dtype(self.code):
             raise DPError("packed weights were made for another compute precision")
         self.P = packed
@@ -421,7 +441,13 @@ class Engine:
         self.vp = _ViTBuffers(NWIN * TOK, vdt, dev, dt, ln_fold=self.ln_fold)     # patch encoder (35 windows)
         # image + FOV encoders, run as one grouped ViT (rows 0..576 image, 577..1153 FOV)
         self.side_vits = ["encoder.image_encoder."] + (["fov.encoder.0."] if self.use_fov else [])
-        self.vs = _ViTBuffers(len(self.side_vits) * TOK, vdt, dev, dt)
+        # their LayerNorms folded into the grouped GEMMs (_vit_blocks_side_folded) when the packed set
+        # holds the folded side weights; a set without them runs the unfolded launches
+        self.side_fold = "encoder.image_encoder.blocks.0.attn.qkv.fold.w" in packed
+        if self.side_fold and not side_ln_fold_enabled():
+            raise DPError("packed weights were made for the other LayerNorm path (DP_ABLATE differs from "
+                          "when they were packed)")
+        self.vs = _ViTBuffers(len(self.side_vits) * TOK, vdt, dev, dt, part=self.side_fold)
         self.vi = _ViTRows(self.vs, 0, TOK)
         self.vf = _ViTRows(self.vs, TOK, 2 * TOK) if self.use_fov else None
         # merged encoder maps (NHWC)
@@ -528,10 +554,15 @@ class Engine:
             not a_rows); per-problem bias / gamma / pos given as key suffixes in kw."""
             per = {k: kw.pop(k) for k in ("bias", "gamma", "pos") if isinstance(kw.get(k), str)}
             A_off = kw.pop("A_off", 0)
+            ln_in, ln_out = kw.pop("ln_in", None), kw.pop("ln_out", False)
             groups = []
             for g, pre in enumerate(pres):
                 d = dict(A=A, B=P[pre + key], C=C, A_off=A_off + (g * M * K if a_rows else 0), C_off=g * M * N)
                 d.update({k: P[pre + v] for k, v in per.items()})
+                if ln_in:       # folded-LN consumer: the rows' statistics + this ViT's column sums
+                    d["ln_in"] = (buf.part[g * M:], P[pre + ln_in])
+                if ln_out:      # folded-LN producer: the new rows in 16 bits + their statistics
+                    d["ln_out"] = (buf.h[g * M:], buf.part[g * M:])
                 groups.append(d)
             ops.gemm_grouped(groups, M=kw.pop("M", M), N=N, K=K, **kw)
 
@@ -545,10 +576,35 @@ class Engine:
             row_off=1)
         for g, pre in enumerate(pres):
             ops.vit_cls_rows(buf.x[g * M:], P[pre + "cls"], P[pre + "pos"], n_img)
-        if G == 1 and buf.part is not None:
+        if G == 1 and buf.xl is not None:
             yield from self._vit_blocks_folded(pres[0], buf, M, hooks)
             return
         yield
+        if buf.part is not None:
+            # the side encoders with norm1 / norm2 folded into the grouped GEMMs' epilogues: the residual
+            # stream stays fp32 in x; proj / fc2 also write the 16-bit rows h + their chunk statistics
+            # (block 0: one statistics pass over all G ViTs' rows, no affine parameters in it), qkv / fc1
+            # run on the folded weights -- 5 launches per Block instead of 7
+            ops.layernorm_stats(buf.x, buf.h, buf.part, G * M, D)
+            for i in range(DEPTH):
+                b = f"blocks.{i}."
+                lin(buf.h, b + "attn.qkv.fold.w", buf.qkv, 3 * D, D, bias=b + "attn.qkv.fold.b",
+                    ln_in=b + "attn.qkv.fold.s")
+                if "attn" not in _ABLATE:
+                    ops.attention(buf.qkv, buf.a, G * n_img, TOK, HEADS, D // HEADS, log2q=True)
+                lin(buf.a, b + "attn.proj.weight", buf.x, D, D, bias=b + "attn.proj.bias", gamma=b + "ls1.gamma",
+                    accumulate=True, ln_out=True)
+                lin(buf.h, b + "mlp.fc1.fold.w", buf.m, MLP_DIM, D, bias=b + "mlp.fc1.fold.b", act=DP_ACT_GELU,
+                    ln_in=b + "mlp.fc1.fold.s")
+                last = i == DEPTH - 1      # the final norm reads x itself
+                lin(buf.m, b + "mlp.fc2.weight", buf.x, D, MLP_DIM, bias=b + "mlp.fc2.bias", gamma=b + "ls2.gamma",
+                    accumulate=True, ln_out=not last)
+                if hooks and i in hooks:
+                    hooks[i]()
+                if last:
+                    norm("norm", buf.out)
+                yield
+            return
         for i in range(DEPTH):
             b = f"blocks.{i}."
             if ln_on:

@@ -230,15 +230,34 @@ def gemm_grouped(groups, **common) -> None:
     """dp_gemm_grouped: len(groups) dense GEMMs of one shape in one launch.  Each entry of `groups`
     is a dict with that problem's tensors -- A, B, C and optionally bias, gamma, pos, R1, R2 and the
     element offsets A_off / C_off -- and `common` holds the shared arguments of `gemm` (M, N, K,
-    act, accumulate, row_group, ...).  Same result as one `gemm` call per problem."""
+    act, accumulate, row_group, ...).  Same result as one `gemm` call per problem.
+
+    Folded LayerNorm per problem (dp_mi355x.h, dp_gemm_grouped): `ln_out=(xb, part)` -- the fp32
+    residual accumulate also writes its rows in 16 bits and their chunk statistics; `ln_in=(part,
+    colsum)` -- the consumer over un-normalised rows with folded B / bias; each tensor starts at
+    that problem's first row (pass slices).  `ln_eps` in `common`."""
     arr = (GemmArgs * len(groups))()
+    M, N, K = common["M"], common["N"], common["K"]
     for i, g in enumerate(groups):
         kw = dict(common)
         kw.update(g)
         A, B, C = kw.pop("A"), kw.pop("B"), kw.pop("C")
+        ln_out, ln_in, ln_eps = kw.pop("ln_out", None), kw.pop("ln_in", None), kw.pop("ln_eps", 1e-6)
         arr[i] = _gemm_args(A, B, C, **kw)
-        _check_gemm_extents(A, B, C, arr[i], kw.get("A_off", 0), kw.get("C_off", 0), None, None, False, False)
-    M, N, K = common["M"], common["N"], common["K"]
+        a = arr[i]      # (a view of the array's element: the ln_* fields below land in it)
+        _check_gemm_extents(A, B, C, a, kw.get("A_off", 0), kw.get("C_off", 0), None, None, False, False)
+        if ln_out is not None:
+            xb, part = ln_out
+            if xb.numel() < (M - 1) * a.ldc + N or xb.dtype != B.dtype or part.numel() < M * (N // 128) * 2 or \
+                    part.dtype != torch.float32:
+                raise _lib.DPError("dp_gemm_grouped: ln_out buffers too small or of the wrong type")
+            a.ln_xb_out, a.ln_part_out = xb.data_ptr(), part.data_ptr()
+        if ln_in is not None:
+            part, colsum = ln_in
+            if part.numel() < M * (K // 128) * 2 or part.dtype != torch.float32 or colsum.numel() < N or \
+                    colsum.dtype != torch.float32:
+                raise _lib.DPError("dp_gemm_grouped: ln_in buffers too small or of the wrong type")
+            a.ln_part_in, a.ln_colsum, a.ln_eps = part.data_ptr(), colsum.data_ptr(), float(ln_eps)
     with _Timed("gemm", 2.0 * M * N * K * len(groups), (M, N, K), groups[0]["B"].dtype):
         check(_lib.load().dp_gemm_grouped(arr, len(groups), _stream(groups[0]["C"])), "dp_gemm_grouped")
 

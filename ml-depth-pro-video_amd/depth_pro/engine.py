@@ -46,6 +46,32 @@ def side_ln_fold_enabled() -> bool:
     return ln_fold_enabled() and "sideln" not in _ABLATE
 
 
+# A ViT's LayerNorm path: where norm1 / norm2 live and what the residual GEMMs (proj / fc2) also
+# write for them.  It decides the packed weights (pack_vit), the buffers (_ViTBuffers) and the launches
+# (Engine._vit).
+LN_UNFOLDED = "unfolded"   # LayerNorm launches of their own (only under the timing ablations)
+LN_FOLDED = "folded"       # in the qkv / fc1 epilogues; fp32 stream `x`, proj / fc2 also write `h` + `part` (side pair)
+LN_SPLIT = "split"         # folded, the stream itself is `h` + `xl`; proj / fc2 also write `part` + `rs` (patch encoder)
+PATCH_VIT = "encoder.patch_encoder."
+
+
+def ln_mode_enabled(vit: str) -> str:
+    """The LayerNorm path that DP_ABLATE selects for the ViT with weight prefix `vit`."""
+    if vit == PATCH_VIT:
+        return LN_SPLIT if ln_fold_enabled() else LN_UNFOLDED
+    return LN_FOLDED if side_ln_fold_enabled() else LN_UNFOLDED
+
+
+def vit_ln_mode(packed: Dict[str, object], vit: str) -> str:
+    """The LayerNorm path of ViT `vit` of a packed set: whether it holds the folded qkv / fc1 says which
+    path it was packed for, and that must be the one this process runs (`ln_mode_enabled`)."""
+    mode = ln_mode_enabled(vit)
+    if (vit + "blocks.0.attn.qkv.fold.w" in packed) != (mode != LN_UNFOLDED):
+        raise DPError("packed weights were made for the other LayerNorm path (DP_ABLATE differs from "
+                      "when they were packed)")
+    return mode
+
+
 NWIN = 35
 TOK = TOKENS            # 577
 PTOK = TOKENS - 1       # 576
@@ -163,8 +189,8 @@ def pack_vit(sd: Dict[str, torch.Tensor], vit: str, device: torch.device, vdt, b
     encoders neither are norm1 / norm2 -- one weight set per LayerNorm path."""
     g = lambda k: sd[k].detach().to(device)  # noqa: E731
     P: Dict[str, object] = {}
-    side = vit != "encoder.patch_encoder."
-    folded = side_ln_fold_enabled() if side else ln_fold_enabled()
+    side = vit != PATCH_VIT
+    folded = ln_mode_enabled(vit) != LN_UNFOLDED
     blocks = range(DEPTH) if blocks is None else blocks
     P[vit + "cls"] = _f32(g(vit + "cls_token")).reshape(D)
     P[vit + "pos"] = _f32(g(vit + "pos_embed")).reshape(TOK, D)
@@ -186,7 +212,7 @@ def pack_vit(sd: Dict[str, torch.Tensor], vit: str, device: torch.device, vdt, b
     if folded:
         # norm1 / norm2 folded into the qkv / fc1 that consume them (ops.fold_layernorm): the
         # residual GEMMs hand the next Linear 16-bit rows + chunk statistics instead of a LayerNorm
-        # pass (Engine._vit_steps); the qkv's log2q gamma rides in the folded weights
+        # pass (Engine._vit); the qkv's log2q gamma rides in the folded weights
         qg = ops.log2q_gamma(HEADS, D // HEADS, device)
         for i in blocks:
             b = f"{vit}blocks.{i}."
@@ -274,24 +300,25 @@ def pack_weights(sd: Dict[str, torch.Tensor], device: torch.device, dtype_code) 
 
 # ---------------------------------------------------------------------- engine
 class _ViTBuffers:
-    def __init__(self, rows: int, dt, dev, out_dt=None, ln_fold: bool = False, part: bool = False):
+    def __init__(self, rows: int, dt, dev, out_dt=None, mode: str = LN_UNFOLDED):
         self.rows = rows
+        self.mode = mode      # the ViT's LayerNorm path (LN_*): what Engine._vit launches on these buffers
         self.x = torch.empty(rows, D, dtype=torch.float32, device=dev)
-        # folded LayerNorm: (mean, M2) of each 128-column chunk of the rows in `h` (un-normalised);
-        # `part` alone: the side encoders' fold, whose residual stream stays fp32 in `x`
-        self.part = torch.empty(rows, D // 128, 2, dtype=torch.float32, device=dev) if ln_fold or part else None
+        # folded LayerNorm: (mean, M2) of each 128-column chunk of the rows in `h` (un-normalised); LN_FOLDED
+        # has `part` alone: its residual stream stays fp32 in `x`
+        self.part = torch.empty(rows, D // 128, 2, dtype=torch.float32, device=dev) if mode != LN_UNFOLDED else None
         self.h = torch.empty(rows, D, dtype=dt, device=dev)
-        # folded path: the residual stream between blocks is split, x = h (16 bits) + an 8-bit low
+        # LN_SPLIT: the residual stream between blocks is split, x = h (16 bits) + an 8-bit low
         # part xl (steps of ulp(h) / 256; the proj / fc2 epilogues read and update both, dp_gemm's
         # ln_xl); `x` (fp32) holds it only where an fp32 reader needs it (the patch embed's output, the
         # hooks, the final norm)
-        self.xl = torch.empty(rows, D, dtype=torch.int8, device=dev) if ln_fold else None
+        self.xl = torch.empty(rows, D, dtype=torch.int8, device=dev) if mode == LN_SPLIT else None
         # (ABI 13): every row's (rstd, -rstd * mean), merged by the proj / fc2 producers' last
         # workgroup per row tile for the qkv / fc1 consumers on the persistent engine; padded to whole
         # 256-row tiles, which is more than needed: the consumer clamps rows past M to the pair holding
         # row M - 1, so dp_gemm asks only for M rounded up to an even row count
         self.rs = (torch.empty((rows + 255) // 256 * 256, 2, dtype=torch.float32, device=dev)
-                   if ln_fold else None)
+                   if mode == LN_SPLIT else None)
         self.qkv = torch.empty(rows, 3 * D, dtype=dt, device=dev)
         self.a = torch.empty(rows, D, dtype=dt, device=dev)
         self.m = torch.empty(rows, MLP_DIM, dtype=dt, device=dev)
@@ -432,22 +459,11 @@ class Engine:
         S = IMG_SIZE
         self.x0 = e(3, S, S, dtype=torch.float32)           # network input (normalized, 1536^2)
         self.cols = e(NWIN * PTOK, 768, dtype=vdt)
-        # patch encoder LayerNorms folded into its GEMMs (pack_weights, _vit): whichever path the packed
-        # set was made for (DP_LN_FOLD / ablations at pack time, ln_fold_enabled)
-        self.ln_fold = "encoder.patch_encoder.blocks.0.attn.qkv.fold.w" in packed
-        if self.ln_fold != ln_fold_enabled():
-            raise DPError("packed weights were made for the other LayerNorm path (DP_ABLATE differs from "
-                          "when they were packed)")
-        self.vp = _ViTBuffers(NWIN * TOK, vdt, dev, dt, ln_fold=self.ln_fold)     # patch encoder (35 windows)
+        # each ViT's LayerNorm path is the one its packed weights were made for (vit_ln_mode; _vit)
+        self.vp = _ViTBuffers(NWIN * TOK, vdt, dev, dt, vit_ln_mode(packed, PATCH_VIT))   # patch encoder (35 windows)
         # image + FOV encoders, run as one grouped ViT (rows 0..576 image, 577..1153 FOV)
         self.side_vits = ["encoder.image_encoder."] + (["fov.encoder.0."] if self.use_fov else [])
-        # their LayerNorms folded into the grouped GEMMs (_vit_blocks_side_folded) when the packed set
-        # holds the folded side weights; a set without them runs the unfolded launches
-        self.side_fold = "encoder.image_encoder.blocks.0.attn.qkv.fold.w" in packed
-        if self.side_fold and not side_ln_fold_enabled():
-            raise DPError("packed weights were made for the other LayerNorm path (DP_ABLATE differs from "
-                          "when they were packed)")
-        self.vs = _ViTBuffers(len(self.side_vits) * TOK, vdt, dev, dt, part=self.side_fold)
+        self.vs = _ViTBuffers(len(self.side_vits) * TOK, vdt, dev, dt, vit_ln_mode(packed, self.side_vits[0]))
         self.vi = _ViTRows(self.vs, 0, TOK)
         self.vf = _ViTRows(self.vs, TOK, 2 * TOK) if self.use_fov else None
         # merged encoder maps (NHWC)
@@ -530,45 +546,89 @@ class Engine:
     # ------------------------------------------------------------------ ViT
     def _vit(self, pres, buf: _ViTBuffers, n_img: int, cols_off_rows: int, hooks=None):
         """timm forward_features (vit_factory.py:97-99 -> vision_transformer.py): patch embed + cls /
-        pos, 24 Blocks, final norm; `hooks[i]()` runs after block i (encoder.py:133-144)."""
-        for _ in self._vit_steps(pres, buf, n_img, cols_off_rows, hooks):
-            pass
-
-    def _vit_steps(self, pres, buf: _ViTBuffers, n_img: int, cols_off_rows: int, hooks=None):
-        """`_vit` as a generator: yields after the embedding and after each Block (the final norm
-        runs on the last step) -- lets a caller issue another stream's ViT block by block.
+        pos, 24 Blocks, final norm; `hooks[i]()` runs after block i (encoder.py:133-144).
 
         `pres`: the weight prefixes of G ViTs of one shape over the same im2col rows (G = 2: the
         image and FOV encoders, encoder.py:308-311 and fov.py:66-72); ViT g owns rows
         [g * n_img * 577, (g + 1) * n_img * 577) of `buf`, and every op runs as ONE grouped launch
-        for the G of them (dp_gemm_grouped / dp_layernorm_grouped, attention over G * n_img)."""
-        P, M = self.P, n_img * TOK
-        G = len(pres)
-        # ablations (A/B timing only): 'ln' / 'vitgemm' everywhere; 'sideln': the grouped side pair's
-        # LayerNorm launches only (is the side chain's latency on the frame's critical path?)
+        for the G of them (dp_gemm_grouped / dp_layernorm_grouped, attention over G * n_img).
+
+        `buf.mode` says where the Blocks' norm1 / norm2 live.  LN_UNFOLDED: launches of their own, 7 per
+        Block.  LN_FOLDED / LN_SPLIT: folded across the GEMM boundary (dp_gemm_args.ln_*), 5 per Block: `h`
+        carries the un-normalised residual rows in 16 bits and `part` their 128-column chunk statistics,
+        written by the producer (block 0: dp_layernorm_stats; then every proj / fc2 epilogue beside its
+        residual update); qkv / fc1 run on the folded weights (ops.fold_layernorm) and apply LN's per-row
+        mean / rstd in their epilogue.  Same arithmetic as LN -> Linear up to where the 16-bit rounding
+        falls (x instead of LN(x); tools/ln_fold_emul.py: rel-L1 vs fp32 unchanged, 2.377e-3 vs 2.379e-3
+        bf16).  LN_SPLIT (G = 1) also keeps the stream itself as `h` + `xl` and has the producers merge every
+        row's statistics into `rs` (ABI 13) for the persistent consumers; those forms exist in dp_gemm only,
+        so its Blocks' GEMMs are dp_gemm calls."""
+        P, M, G = self.P, n_img * TOK, len(pres)
+        hooks = hooks or {}
+        split, folded = buf.mode == LN_SPLIT, buf.mode != LN_UNFOLDED
+        # ablations (A/B timing only; 'ln' / 'vitgemm' / 'sideln' leave the ViTs they name LN_UNFOLDED, whose
+        # launches they drop): 'ln' / 'vitgemm' everywhere; 'sideln': the grouped side pair's LayerNorm
+        # launches only (is the side chain's latency on the frame's critical path?)
         ln_on = "ln" not in _ABLATE and not (G > 1 and "sideln" in _ABLATE)
         gemm_on = "vitgemm" not in _ABLATE
+        attn_on = "attn" not in _ABLATE
 
-        def lin(A, key, C, N, K, a_rows=True, **kw):
+        def lin(A, key, C, N, K, a_rows=True, one=False, ln_in=None, ln_out=None, **kw):
             """The G problems' `key` Linear: A rows / C rows of problem g at g * M (A shared when
-            not a_rows); per-problem bias / gamma / pos given as key suffixes in kw."""
+            not a_rows); per-problem bias / gamma / pos given as key suffixes in kw.  `ln_in` = (key of
+            the folded weights' column sums, read `part`?): a folded-LN consumer; `ln_out` = write `part`?
+            (None: no producer): a folded-LN producer, the new rows in 16 bits to `h`.  `one`: a dp_gemm
+            call (G = 1), else one grouped launch."""
             per = {k: kw.pop(k) for k in ("bias", "gamma", "pos") if isinstance(kw.get(k), str)}
             A_off = kw.pop("A_off", 0)
-            ln_in, ln_out = kw.pop("ln_in", None), kw.pop("ln_out", False)
             groups = []
             for g, pre in enumerate(pres):
                 d = dict(A=A, B=P[pre + key], C=C, A_off=A_off + (g * M * K if a_rows else 0), C_off=g * M * N)
                 d.update({k: P[pre + v] for k, v in per.items()})
-                if ln_in:       # folded-LN consumer: the rows' statistics + this ViT's column sums
-                    d["ln_in"] = (buf.part[g * M:], P[pre + ln_in])
-                if ln_out:      # folded-LN producer: the new rows in 16 bits + their statistics
-                    d["ln_out"] = (buf.h[g * M:], buf.part[g * M:])
+                if ln_in is not None:
+                    d["ln_in"] = (buf.part[g * M:] if ln_in[1] else None, P[pre + ln_in[0]])
+                if ln_out is not None:
+                    d["ln_out"] = (buf.h[g * M:], buf.part[g * M:] if ln_out else None)
                 groups.append(d)
-            ops.gemm_grouped(groups, M=kw.pop("M", M), N=N, K=K, **kw)
+            if one:
+                ops.gemm(**groups[0], M=kw.pop("M", M), N=N, K=K, **kw)
+            else:
+                ops.gemm_grouped(groups, M=kw.pop("M", M), N=N, K=K, **kw)
 
         def norm(key, out):
-            ops.layernorm_grouped(buf.x, [P[pre + key + ".weight"] for pre in pres],
-                                  [P[pre + key + ".bias"] for pre in pres], out, M, D)
+            if split:       # the final norm
+                ops.layernorm(buf.x, P[pres[0] + key + ".weight"], P[pres[0] + key + ".bias"], out, M, D)
+            else:
+                ops.layernorm_grouped(buf.x, [P[pre + key + ".weight"] for pre in pres],
+                                      [P[pre + key + ".bias"] for pre in pres], out, M, D)
+
+        def ln_lin(b, ln, name, C, N, rs_in, **kw):
+            """Block Linear `name` (qkv, fc1) of the stream's LayerNorm `ln`: the norm as a launch of its
+            own, or folded into the Linear's weights and epilogue (`rs_in`: `rs` holds these rows' statistics)."""
+            if folded:
+                from_rs = split and rs_in
+                if from_rs:
+                    kw["ln_rs_in"] = buf.rs
+                lin(buf.h, f"{b}{name}.fold.w", C, N, D, one=split, bias=f"{b}{name}.fold.b",
+                    ln_in=(f"{b}{name}.fold.s", not from_rs), **kw)
+                return
+            if ln_on:
+                norm(b + ln, buf.h)
+            if gemm_on:
+                lin(buf.h, f"{b}{name}.weight", C, N, D, bias=f"{b}{name}.bias", **kw)
+
+        def res_lin(A, b, name, ls, K, C, stats=True):
+            """x += `ls`.gamma * Block Linear `name` (proj, fc2) -- which in the folded modes hands the next
+            LayerNorm its input: the new rows in `h` and, with `stats`, their statistics (`part`, `rs`)."""
+            if not gemm_on:
+                return
+            kw = {}
+            if split:
+                kw = dict(ln_out=stats, ln_xl=buf.xl, ln_rs_out=buf.rs if stats else None)
+            elif folded and stats:
+                kw = dict(ln_out=True)
+            lin(A, f"{b}{name}.weight", C, D, K, one=split, bias=f"{b}{name}.bias", gamma=f"{b}{ls}.gamma",
+                accumulate=True, **kw)
 
         # patch embed (k16 s16 conv as GEMM over the im2col rows) + bias + pos -> rows 1..576
         lin(self.cols, "pe.w", buf.x, D, 768, a_rows=False, M=n_img * PTOK, A_off=cols_off_rows * 768,
@@ -576,99 +636,27 @@ class Engine:
             row_off=1)
         for g, pre in enumerate(pres):
             ops.vit_cls_rows(buf.x[g * M:], P[pre + "cls"], P[pre + "pos"], n_img)
-        if G == 1 and buf.xl is not None:
-            yield from self._vit_blocks_folded(pres[0], buf, M, hooks)
-            return
-        yield
-        if buf.part is not None:
-            # the side encoders with norm1 / norm2 folded into the grouped GEMMs' epilogues: the residual
-            # stream stays fp32 in x; proj / fc2 also write the 16-bit rows h + their chunk statistics
-            # (block 0: one statistics pass over all G ViTs' rows, no affine parameters in it), qkv / fc1
-            # run on the folded weights -- 5 launches per Block instead of 7
-            ops.layernorm_stats(buf.x, buf.h, buf.part, G * M, D)
-            for i in range(DEPTH):
-                b = f"blocks.{i}."
-                lin(buf.h, b + "attn.qkv.fold.w", buf.qkv, 3 * D, D, bias=b + "attn.qkv.fold.b",
-                    ln_in=b + "attn.qkv.fold.s")
-                if "attn" not in _ABLATE:
-                    ops.attention(buf.qkv, buf.a, G * n_img, TOK, HEADS, D // HEADS, log2q=True)
-                lin(buf.a, b + "attn.proj.weight", buf.x, D, D, bias=b + "attn.proj.bias", gamma=b + "ls1.gamma",
-                    accumulate=True, ln_out=True)
-                lin(buf.h, b + "mlp.fc1.fold.w", buf.m, MLP_DIM, D, bias=b + "mlp.fc1.fold.b", act=DP_ACT_GELU,
-                    ln_in=b + "mlp.fc1.fold.s")
-                last = i == DEPTH - 1      # the final norm reads x itself
-                lin(buf.m, b + "mlp.fc2.weight", buf.x, D, MLP_DIM, bias=b + "mlp.fc2.bias", gamma=b + "ls2.gamma",
-                    accumulate=True, ln_out=not last)
-                if hooks and i in hooks:
-                    hooks[i]()
-                if last:
-                    norm("norm", buf.out)
-                yield
-            return
+        if folded:
+            # the stream enters as fp32: one statistics pass over all G ViTs' rows (no affine parameters in
+            # it) writes h + part for block 0, and the split stream's first xl
+            ops.layernorm_stats(buf.x, buf.h, buf.part, G * M, D, xl=buf.xl)
         for i in range(DEPTH):
             b = f"blocks.{i}."
-            if ln_on:
-                norm(b + "norm1", buf.h)
-            if gemm_on:
-                lin(buf.h, b + "attn.qkv.weight", buf.qkv, 3 * D, D, bias=b + "attn.qkv.bias", gamma=self.qkv_gamma)
-            if "attn" not in _ABLATE:
+            last = i == DEPTH - 1      # the final norm reads x itself: no statistics for a next Block
+            # (block 0 reads `part`, not `rs`: the statistics pass wrote `part` only)
+            # (the log2q gamma rides in the folded weights)
+            ln_lin(b, "norm1", "attn.qkv", buf.qkv, 3 * D, rs_in=i > 0, gamma=None if folded else self.qkv_gamma,
+                   tile=self.qkv_tile if split else 0)
+            if attn_on:
                 ops.attention(buf.qkv, buf.a, G * n_img, TOK, HEADS, D // HEADS, log2q=True)
-            if gemm_on:
-                lin(buf.a, b + "attn.proj.weight", buf.x, D, D, bias=b + "attn.proj.bias", gamma=b + "ls1.gamma",
-                    accumulate=True)
-            if ln_on:
-                norm(b + "norm2", buf.h)
-            if gemm_on:
-                lin(buf.h, b + "mlp.fc1.weight", buf.m, MLP_DIM, D, bias=b + "mlp.fc1.bias", act=DP_ACT_GELU)
-            if gemm_on:
-                lin(buf.m, b + "mlp.fc2.weight", buf.x, D, MLP_DIM, bias=b + "mlp.fc2.bias", gamma=b + "ls2.gamma",
-                    accumulate=True)
-            if hooks and i in hooks:
+            res_lin(buf.a, b, "attn.proj", "ls1", D, None if split else buf.x)
+            ln_lin(b, "norm2", "mlp.fc1", buf.m, MLP_DIM, rs_in=True, act=DP_ACT_GELU)
+            # the split stream's fp32 rows only where they are read: the hooks (merge_windows), the final norm
+            res_lin(buf.m, b, "mlp.fc2", "ls2", MLP_DIM, buf.x if not split or last or i in hooks else None,
+                    stats=not last)
+            if i in hooks:
                 hooks[i]()
-            if i == DEPTH - 1:
-                norm("norm", buf.out)
-            yield
-
-    def _vit_blocks_folded(self, pre: str, buf: _ViTBuffers, M: int, hooks=None):
-        """The 24 Blocks with norm1 / norm2 folded across the GEMM boundary (dp_gemm_args.ln_*):
-        `h` carries the un-normalised residual rows in 16 bits and `part` their 128-column chunk
-        statistics, written by the producer (block 0: dp_layernorm_stats; then every proj / fc2
-        epilogue beside its split-residual update); qkv / fc1 run on the folded weights
-        (ops.fold_layernorm) and apply LN's per-row mean / rstd in their epilogue.  Same
-        arithmetic as LN -> Linear up to where the 16-bit rounding falls (x instead of LN(x);
-        tools/ln_fold_emul.py: rel-L1 vs fp32 unchanged, 2.377e-3 vs 2.379e-3 bf16).  A generator
-        like _vit_steps."""
-        P = self.P
-        n_img = M // TOK
-        # the stream enters as fp32 (patch embed + cls rows): split it into h + xl, with the stats
-        ops.layernorm_stats(buf.x, buf.h, buf.part, M, D, xl=buf.xl)
-        yield
-        qkv_tile = self.qkv_tile
-        rs = buf.rs       # producer-merged row statistics (ABI 13), for the persistent consumers
-        for i in range(DEPTH):
-            b = f"{pre}blocks.{i}."
-            rs_q = rs if i > 0 else None     # block 0: the stats pass wrote `part` only
-            ops.gemm(buf.h, P[b + "attn.qkv.fold.w"], buf.qkv, M=M, N=3 * D, K=D, bias=P[b + "attn.qkv.fold.b"],
-                     ln_in=(None if rs_q is not None else buf.part, P[b + "attn.qkv.fold.s"]), ln_rs_in=rs_q,
-                     tile=qkv_tile)
-            if "attn" not in _ABLATE:
-                ops.attention(buf.qkv, buf.a, n_img, TOK, HEADS, D // HEADS, log2q=True)
-            ops.gemm(buf.a, P[b + "attn.proj.weight"], None, M=M, N=D, K=D,
-                     bias=P[b + "attn.proj.bias"], gamma=P[b + "ls1.gamma"], accumulate=True,
-                     ln_out=(buf.h, buf.part), ln_xl=buf.xl, ln_rs_out=rs)
-            ops.gemm(buf.h, P[b + "mlp.fc1.fold.w"], buf.m, M=M, N=MLP_DIM, K=D, bias=P[b + "mlp.fc1.fold.b"],
-                     act=DP_ACT_GELU, ln_in=(None, P[b + "mlp.fc1.fold.s"]), ln_rs_in=rs)
-            last = i == DEPTH - 1    # the final norm reads x itself
-            # fp32 rows only where they are read: the hooks (merge_windows) and the final norm
-            need_x = last or bool(hooks and i in hooks)
-            ops.gemm(buf.m, P[b + "mlp.fc2.weight"], buf.x if need_x else None, M=M, N=D, K=MLP_DIM,
-                     bias=P[b + "mlp.fc2.bias"], gamma=P[b + "ls2.gamma"], accumulate=True,
-                     ln_out=(buf.h, None if last else buf.part), ln_xl=buf.xl, ln_rs_out=None if last else rs)
-            if hooks and i in hooks:
-                hooks[i]()
-            if last:
-                ops.layernorm(buf.x, P[pre + "norm.weight"], P[pre + "norm.bias"], buf.out, M, D)
-            yield
+        norm("norm", buf.out)
 
     # -------------------------------------------------------- conv helpers
     def _conv3(self, x, s_in, cin, w, out, cout, bias=None, relu_a=False, act=0, R1=None, R2=None,
@@ -720,14 +708,8 @@ class Engine:
     def _side_encoders(self):
         """Image encoder ViT on x2 (encoder.py:308-311) and FOV encoder ViT (fov.py:66-72) as one
         grouped ViT, then the lowres upsample into `cat` and the FOV Linear (fov.py:45-47)."""
-        for _ in self._side_steps():
-            pass
-
-    def _side_steps(self):
-        """_side_encoders as a generator: the embedding, then one step per Block (the final norm
-        with the last), then the lowres upsample + FOV Linear after the last yield."""
         P, e = self.P, "encoder."
-        yield from self._vit_steps(self.side_vits, self.vs, 1, 34 * PTOK)
+        self._vit(self.side_vits, self.vs, 1, 34 * PTOK)
         ops.merge_windows(self.vi.out, 0, 1, 0, self.g)
         self._deconv(self.g, 24, D, P[e + "upsample_lowres.w"], self.cat, D, bias=P[e + "upsample_lowres.b"],
                      C_off=D, ldc=2 * D)
@@ -808,7 +790,7 @@ class Engine:
         # blocks 6..23: 47.88 / 47.76 vs 48.17 / 48.07 fps, profiles/r05g_lat_early/)
         hooks = {5: lambda: ops.merge_windows(vp.x, 0, 5, 3, self.lat0),
                  11: lambda: ops.merge_windows(vp.x, 0, 5, 3, self.lat1)}
-        self._vit(["encoder.patch_encoder."], vp, NWIN, 0, hooks)
+        self._vit([PATCH_VIT], vp, NWIN, 0, hooks)
         ops.merge_windows(vp.out, 0, 5, 3, self.f0)
         ops.merge_windows(vp.out, 25, 3, 6, self.f1)
         ops.merge_windows(vp.out, 34, 1, 0, self.f2)

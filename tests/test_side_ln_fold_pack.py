@@ -17,6 +17,61 @@ from depth_pro.spec import EMBED_DIM, HEADS, vit_spec  # noqa: E402
 from depth_pro.weights import synthetic_tensor  # noqa: E402
 
 BLOCKS = (0, 23)
+PKG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ml-depth-pro-video_amd")
+
+# What a child process does under its own DP_ABLATE (read at import): pack two Blocks of the patch and the
+# image encoder, print each set's LayerNorm path (engine.vit_ln_mode) and key names, and -- given the key
+# names of sets packed under another DP_ABLATE as argv[1] -- what vit_ln_mode says of those.
+CHILD = """
+import json, sys, torch
+sys.path.insert(0, %r)
+from depth_pro import engine
+from depth_pro.spec import vit_spec
+from depth_pro.weights import synthetic_tensor
+foreign = json.loads(sys.argv[1]) if len(sys.argv) > 1 else {}
+out = {}
+for vit in ("encoder.patch_encoder.", "encoder.image_encoder."):
+    keep = tuple(f"{vit}blocks.{i}." for i in (0, 1))
+    sd = {k: synthetic_tensor(k, s) for k, s in vit_spec(vit).items() if "blocks." not in k or k.startswith(keep)}
+    P = engine.pack_vit(sd, vit, torch.device("cpu"), torch.bfloat16, blocks=(0, 1))
+    out[vit] = {"mode": engine.vit_ln_mode(P, vit), "keys": sorted(P)}
+    if vit in foreign:
+        try:
+            out[vit]["foreign"] = engine.vit_ln_mode(dict.fromkeys(foreign[vit]), vit)
+        except engine.DPError as e:
+            out[vit]["foreign"] = "DPError: " + str(e)
+print(json.dumps(out))
+""" % PKG
+
+
+def _packed_modes(ablate, foreign=None):
+    import json
+    import subprocess
+
+    env = dict(os.environ, DP_ABLATE=ablate)
+    argv = [sys.executable, "-c", CHILD] + ([json.dumps({v: d["keys"] for v, d in foreign.items()})] if foreign else [])
+    p = subprocess.run(argv, capture_output=True, text=True, env=env, timeout=300)
+    assert p.returncode == 0, p.stderr
+    return json.loads(p.stdout.splitlines()[-1])
+
+
+def test_vit_ln_mode_of_packed_sets():
+    """engine.vit_ln_mode: split / folded / unfolded for sets that pack_vit made under the matching
+    DP_ABLATE, DPError where the set and the environment disagree (patch and side prefix)."""
+    patch, image = "encoder.patch_encoder.", "encoder.image_encoder."
+    plain = _packed_modes("")
+    assert (plain[patch]["mode"], plain[image]["mode"]) == ("split", "folded")
+    for ablate in ("ln", "vitgemm"):        # both unfolded; the default's folded sets are refused
+        got = _packed_modes(ablate, plain)
+        assert (got[patch]["mode"], got[image]["mode"]) == ("unfolded", "unfolded")
+        assert got[patch]["foreign"].startswith("DPError") and got[image]["foreign"].startswith("DPError")
+    unfolded = got
+    got = _packed_modes("sideln", plain)    # the side encoders alone unfolded
+    assert (got[patch]["mode"], got[image]["mode"]) == ("split", "unfolded")
+    assert got[patch]["foreign"] == "split" and got[image]["foreign"].startswith("DPError")
+    got = _packed_modes("", unfolded)       # and unfolded sets where the folded paths run
+    assert got[patch]["foreign"].startswith("DPError") and got[image]["foreign"].startswith("DPError")
+    assert "other LayerNorm path" in got[patch]["foreign"]
 
 
 @pytest.mark.parametrize("vit", ["encoder.image_encoder.", "fov.encoder.0."])
